@@ -11,8 +11,11 @@ Headline workload (config.workload): BASELINE.json configs[3] shape — syntheti
 vector — does not).  `--scaling strong` keeps the corpus at 1M pairs in total and gives every rank 1/N of it.
 `--config NAME` makes another workload the headline.
 
-At N = 1 the same process then runs the other workloads one after another and attaches each to the line as
-`"secondary": {name: {...}}` with its own `roofline`, `cpu_baseline` and `kernel_ms` (`--no-secondary` skips them):
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the last step's outputs
+(--dump-outputs DIR: DIR/<name>.npy, float64, a fixed seeded sample of the larger arrays) and print the line.
+Everything else is measured under --full: the `cpu_baseline` legs, the exchange measurement, the samplers' exact chains,
+and at N = 1 the other workloads, run one after another and attached to the line as
+`"secondary": {name: {...}}` with their own `roofline`, `cpu_baseline` and `kernel_ms` (`--no-secondary` skips them):
   c4a   config 4's sizes on a clustered transducer whose lattices are ambiguous (3 in-arcs per lattice state)
   amb   the tutorial's tagging cascade x400 through the carmel front end
   c2    BASELINE.json configs[1]
@@ -24,11 +27,11 @@ At N = 1 the same process then runs the other workloads one after another and at
 The line printed is COMPACT (the driver keeps the last 2 000 characters): the headline in full, every secondary as
 {ms_per_step, kernel_ms, frac, traffic, cpu, parity, value}; the complete objects go to --full-out (a file).
 
-The `cpu_baseline` leg of every synthetic EM workload also CHECKS the GPU: the oracle's per-pair ln p and per-arc
+The `cpu_baseline` leg (--full) of every synthetic EM workload also CHECKS the GPU: the oracle's per-pair ln p and per-arc
 counts on the timed sample are compared with a GPU trainer's on the same pairs (rtol 1e-7); `parity_checked_pairs`
 says how many pairs that was, and a mismatch fails the run.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 with a `roofline` object (and, under --full, `cpu_baseline`).
 """
 import argparse
 import json
@@ -243,7 +246,7 @@ def run_em(name, args, dist=None, rank=0, world=1, local_rank=0, one_device=Fals
     fb = HipForwardBackward(w, c, device=local_rank, host_threads=args.host_threads)
     ls = fb.lattice_stats
     comm, ext_counts, exchange, xinfo = None, None, "none", None
-    loopback = world == 1 and headline and not args.no_exchange_loopback and name in ("c4", "c2", "toy")
+    loopback = world == 1 and headline and args.full and not args.no_exchange_loopback and name in ("c4", "c2", "toy")
     if world > 1 or loopback:
         # the library's own exchange (csrc/exchange.cpp: RCCL -- or the transport of --comm-plugin -- on the communicator's
         # stream beside the count pass).  Should the communicator not come up on every rank, all ranks fall back together
@@ -351,20 +354,25 @@ def run_em(name, args, dist=None, rank=0, world=1, local_rank=0, one_device=Fals
     fence()
     kernel_ms, step_end = [], []
     t0 = time.perf_counter()
+    last_change = None
     for _ in range(steps):
-        step()  # (ends when the host has the M-step's largest change: every step's end is a point on the host's clock)
+        last_change = step()  # (ends when the host has the M-step's largest change: every step's end is a point on the host's clock)
         step_end.append(time.perf_counter())
         kernel_ms.append(fb.last_kernel_ms())
     fence()
     dt = time.perf_counter() - t0
     step_ms = 1e3 * np.diff(np.array([t0] + step_end))
     lp, wlp, n_swept = fb.read_scalars()
+    if headline and rank == 0 and args.dump_outputs:
+        # (weights as probabilities: an arc the M-step gives no count has ln weight -inf, probability 0)
+        dump_outputs(args.dump_outputs, {"arc_probs": np.exp(fb.arc_weights()), "counts": fb.counts(),
+                                         "scalars": np.array([lp, wlp, n_swept, last_change], dtype=np.float64)})
     # the exchange on its own, and what of it the step does not hide: exchange_ms = one iteration's collectives back to
     # back on the communicator's stream (carmel_hip_exchange_measure); exposed_exchange_ms = the step time with the exchange
     # minus the step time of the same trainer without it (a few extra steps, outside the timed region).  At N = 1 both
     # are measured over a loopback communicator of one rank (the collectives still run; they move nothing between GPUs).
     xch = None
-    if comm is not None and ext_counts is None:
+    if args.full and comm is not None and ext_counts is None:
         def timed(fn, n):
             fence()
             t1 = time.perf_counter()
@@ -467,7 +475,7 @@ def run_em(name, args, dist=None, rank=0, world=1, local_rank=0, one_device=Fals
     fb.close()
     if comm is not None:
         comm.close()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import binding as ob  # CPU restatement of the reference: the checker, timed as the baseline
         cap = args.cpu_sample_pairs if headline else {"c2": 50000, "c4a": 20000, "long": 40, "mix": 4000}.get(name, 20000)
         ns = min(cap, c.n_pairs)
@@ -529,7 +537,7 @@ def run_amb(args, steps, warmup, local_rank=0, rank=0):
                         "events on the trainer's stream", "achieved": alg / (k_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": pmc_traffic("amb", None, 1005 * reps), "algorithmic_bytes_per_launch": alg,
                         "kernel_ms": k_ms}}
-    if not args.no_cpu_baseline and rank == 0:
+    if args.full and not args.no_cpu_baseline and rank == 0:
         # the trace of the reference itself: 25.9-26.5 s per iteration on this cascade (commands.trace:5868-5889,
         # unknown hardware, no derivation caching); here the oracle with cached derivations on the 1005 sentences
         oc = [os.path.join(ROOT, "oracle", "oracle_carmel"), "--train-cascade", "-HJ", "-:", "-X", "1.1", "-e", "0", "-M"]
@@ -581,9 +589,6 @@ def run_crp(args, local_rank=0, rank=0, reps_parallel=100, sweeps_parallel=40, s
                 "frac": alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
     par = leg(reps_parallel, sweeps_parallel, ["--crp-parallel"])
-    ex = leg(1, sweeps_exact, [])
-    # the reference's chain 64 times over (--crp-restarts=63: independent runs, gibbs.hpp:880-914) as 64 concurrent wavefronts
-    ex64 = leg(1, max(10, sweeps_exact // 3), ["--crp-restarts=63"])
     out = {"metric": "lattice-arc updates/sec of Gibbs sweeps (sweeps/sec x derivation-lattice arcs)", "value": par["value"], "unit": "arc-updates/s",
            "n_gpus": 1, "steps": par["sweeps"], "warmup": 0, "ms_per_step": par["ms_per_step"], "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f64", "data": "carmel-tutorial tagging.* x%d" % reps_parallel,
@@ -594,8 +599,13 @@ def run_crp(args, local_rank=0, rank=0, reps_parallel=100, sweeps_parallel=40, s
            "roofline": {"bound": "hbm", "kernel": "one sweep = gibbs_lane_kernel (64 lattices a wavefront, one per lane; round 6) + gibbs_lane_recount + gibbs_normsum + gibbs_commit; wall time per sweep "
                         "(difference of two runs of the front end: launch gaps included)", "achieved": par["frac"] * HBM_PEAK_GBS,
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": par["frac"], "traffic": pmc_traffic_crp(par["blocks"]),
-                        "algorithmic_bytes_per_launch": par["algorithmic_bytes_per_launch"]},
-           "exact": {k: ex[k] for k in ("blocks", "sweeps", "ms_per_step", "value", "frac", "lattice_arcs")}}
+                        "algorithmic_bytes_per_launch": par["algorithmic_bytes_per_launch"]}}
+    if not args.full:
+        return out
+    ex = leg(1, sweeps_exact, [])
+    # the reference's chain 64 times over (--crp-restarts=63: independent runs, gibbs.hpp:880-914) as 64 concurrent wavefronts
+    ex64 = leg(1, max(10, sweeps_exact // 3), ["--crp-restarts=63"])
+    out["exact"] = {k: ex[k] for k in ("blocks", "sweeps", "ms_per_step", "value", "frac", "lattice_arcs")}
     out["exact"]["chains64"] = {"runs": 64, "ms_per_chain_sweep": ex64["ms_per_step"], "value": ex64["value"], "unit": "arc-updates/s",
                                 "aggregate_over_one_chain": ex["ms_per_step"] / ex64["ms_per_step"],
                                 "note": "carmel --crp --crp-restarts=63: the 64 runs side by side, a wavefront each (GxArgs::n_chains); value = all chains' sweeps"}
@@ -655,7 +665,7 @@ def run_c3(args, steps, warmup, local_rank=0, rank=0):
            "roofline": {"bound": "mfma", "kernel": kname,
                         "achieved": flops / (k_ms * 1e-3) / 1e12, "peak": F64_PEAK_TFLOPS, "unit": "TFLOP/s",
                         "frac": flops / (k_ms * 1e-3) / 1e12 / F64_PEAK_TFLOPS, "traffic": None, "kernel_ms": k_ms}}
-    if not args.no_cpu_baseline and rank == 0:
+    if args.full and not args.no_cpu_baseline and rank == 0:
         n = 150
         lm2, ch2, co2 = synth.cipher_files(n)
         for name, txt in (("lm2.wfsa", lm2), ("ch2.fst", ch2), ("corpus2", co2)):
@@ -684,8 +694,10 @@ def run_c5(args, steps, warmup, local_rank=0, rank=0, exact_sweeps=1):
     hf.maximize()
     hf.gibbs(max(warmup, 1), alpha=0.1, seed=4 + rank, mode=1)
     t0 = time.perf_counter()
-    hf.gibbs(steps, burnin=steps // 4, alpha=0.1, seed=4 + rank, mode=1)
+    sweep_lp = hf.gibbs(steps, burnin=steps // 4, alpha=0.1, seed=4 + rank, mode=1)
     dt = time.perf_counter() - t0
+    if args.config == "c5" and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rule_probs": np.exp(hf.weights()), "sweep_logprob": sweep_lp})
     sweeps = steps + 1
     n_nodes = float(len(label))
     n_sampled = float(np.mean([len(hf.sample(f)) for f in range(0, args.forests, max(1, args.forests // 2000))])) * args.forests
@@ -704,7 +716,7 @@ def run_c5(args, steps, warmup, local_rank=0, rank=0, exact_sweeps=1):
                         "timed as wall time per sweep around carmel_hip_forests_gibbs (launch gaps included)",
                         "achieved": alg / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": pmc_traffic_c5(args.forests), "algorithmic_bytes_per_launch": alg}}
-    if exact_sweeps:
+    if exact_sweeps and args.full:
         # the reference's chain (forests strictly in order): a parity device, latency-bound by construction
         hf.set_weights(lw)
         hf.maximize()
@@ -724,7 +736,7 @@ def run_c5(args, steps, warmup, local_rank=0, rank=0, exact_sweeps=1):
                                     "aggregate_over_one_chain": v64 / out["exact"]["value"],
                                     "note": "forest-em --crp-restarts=63: 64 independent exact chains in one launch per sweep"}
     hf.close()
-    if not args.no_cpu_baseline and rank == 0:
+    if args.full and not args.no_cpu_baseline and rank == 0:
         from oracle import binding as ob
         from carmel_amd._capi import lib
         nf = min(args.forests, 3000)
@@ -740,6 +752,24 @@ def run_c5(args, steps, warmup, local_rank=0, rank=0, exact_sweeps=1):
                                "sample": "the first %d forests (%d nodes), same parameters; 10 exact (sequential) sweeps of the "
                                          "scalar oracle" % (nf, of.n_nodes)}
     return out
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of a larger output array: 16 MB of float64 each
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy of what the timed path handed back after its last step, float64.  An array longer than DUMP_SAMPLE
+    is written as the same seeded sample of its elements (sorted positions) on every run, so that two builds compare
+    element for element.  Every value written is finite: a non-finite output is an error of the run."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(20261016).choice(a.size, DUMP_SAMPLE, replace=False))]
+        if not np.all(np.isfinite(a)):
+            raise RuntimeError("bench.py: output %s has %d non-finite values" % (name, int((~np.isfinite(a)).sum())))
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def compact_line(out):
@@ -854,8 +884,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="the headline workload only")
     ap.add_argument("--secondary", default="c4a,amb,c2,long,mix,c3,c5,crp", help="which workloads follow the headline at N = 1")
-    ap.add_argument("--full-out", default=None, help="file for the complete JSON (default: gpurun_out/bench_full.json when that directory "
-                                                      "exists or can be made, else none); stdout carries the compact line")
+    ap.add_argument("--full", action="store_true", help="measure everything besides the headline as well: CPU baselines (which also "
+                    "check the GPU against the oracle), the exchange on its own, the samplers' exact chains and, at N = 1, the "
+                    "secondary workloads")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed "
+                    "as DIR/<name>.npy (float64, finite: weights as probabilities; a fixed seeded sample of arrays longer than 2^21)")
+    ap.add_argument("--full-out", default=None, help="file for the complete JSON (default: none); stdout carries the compact line")
     ap.add_argument("--secondary-steps", type=int, default=40)
     ap.add_argument("--cpu-sample-pairs", type=int, default=200000)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-cores CPU leg (0: host cores, at most 64)")
@@ -868,6 +902,8 @@ def main():
     ap.add_argument("--no-exchange-loopback", action="store_true", help="N = 1: skip the loopback measurement of the exchange")
     ap.add_argument("--walk-arcs", default=None, help="min,max arcs of the headline's random walks (default: the config's; other values are experiments)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config in ("c3", "amb", "crp"):
+        ap.error("--dump-outputs: %s runs through the front end, whose outputs stay in its own files" % args.config)
     if args.steps is None:
         # (the EM headline's timed region used to be 20 steps = 9 ms of a c4 run: round-5 verdict.  200 steps, median and p10 / p90 on the line)
         args.steps = 1000 if args.config == "c5" else 20 if args.config in ("c3", "amb", "crp") else 200
@@ -906,7 +942,7 @@ def main():
         if world > 1:
             dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             sec = {}
             for name in [s for s in args.secondary.split(",") if s and s != args.config]:
                 t0 = time.time()
@@ -928,12 +964,6 @@ def main():
             out["secondary"] = sec
         out["bench_wall_s"] = time.time() - t_start
         full = args.full_out
-        if full is None:
-            try:
-                os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-                full = os.path.join(ROOT, "gpurun_out", "bench_full.json")
-            except OSError:
-                full = None
         if full:
             try:
                 with open(full, "w") as fh:

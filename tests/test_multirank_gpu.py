@@ -332,8 +332,8 @@ def test_bench_two_ranks_strong_scaling_is_the_one_rank_run(tmp_path):
     the corpus probability must be the one-rank run's."""
     import json
     bench = os.path.join(ROOT, "bench.py")
-    common = ["--config", "c2", "--pairs", "6000", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-secondary",
-              "--comm-plugin", PLUGIN]
+    common = ["--config", "c2", "--pairs", "6000", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary",
+              "--comm-plugin", PLUGIN]  # (--full: the exchange measured on its own, the loopback one at N = 1 included)
     env = dict(os.environ)
     f1, f2 = str(tmp_path / "one.json"), str(tmp_path / "two.json")  # (stdout carries the compact line, --full-out everything)
     one = subprocess.run([sys.executable, bench, "--gpus", "1", "--full-out", f1] + common, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
@@ -365,7 +365,7 @@ def test_bench_starts_its_own_ranks_without_a_launcher(tmp_path):
     f2 = str(tmp_path / "two.json")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     two = subprocess.run([sys.executable, bench, "--gpus", "2", "--config", "c2", "--pairs", "4000", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-secondary", "--comm-plugin", PLUGIN, "--full-out", f2],
+                          "--full", "--no-cpu-baseline", "--no-secondary", "--comm-plugin", PLUGIN, "--full-out", f2],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=env, timeout=600)
     assert two.returncode == 0, two.stderr[-2000:]
     lines = [l for l in two.stdout.split("\n") if l.startswith("{")]

@@ -1,8 +1,10 @@
 #!/bin/bash
-# the driver's bench command, with the complete objects kept beside the compact line
+# the benchmark with everything it measures (--full), the complete objects kept beside the compact line.
+# usage: bash tools/bench_full.sh [output directory, default bench_out]
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
-( time python bench.py --full-out gpurun_out/bench_full.json ) > gpurun_out/bench_stdout.log 2> gpurun_out/bench_stderr.log
-grep '^{"metric' gpurun_out/bench_stdout.log | tail -1 > gpurun_out/bench_line.json
-cat gpurun_out/bench_line.json
-tail -4 gpurun_out/bench_stderr.log
+OUT=${1:-bench_out}
+mkdir -p "$OUT"
+( time python bench.py --full --full-out "$OUT/bench_full.json" ) > "$OUT/bench_stdout.log" 2> "$OUT/bench_stderr.log"
+grep '^{"metric' "$OUT/bench_stdout.log" | tail -1 > "$OUT/bench_line.json"
+cat "$OUT/bench_line.json"
+tail -4 "$OUT/bench_stderr.log"

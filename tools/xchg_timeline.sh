@@ -7,7 +7,7 @@ FORM=${2:-sharded}
 OUT=/tmp/r5_xtl
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --exchange-chunks $K --exchange $FORM > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --exchange-chunks $K --exchange $FORM > $OUT/log 2>&1
 f=$(find $OUT -name '*kernel_trace.csv' | head -1)
 python3 - "$f" <<'P'
 import csv,sys
