@@ -38,6 +38,8 @@ SYMBOLS = [
     "carmel_hip_comm_abort", "carmel_hip_comm_transport_name", "carmel_hip_comm_create_custom", "carmel_hip_comm_set_sendrecv", "carmel_hip_comm_selftest", "carmel_hip_exchange_plan",
     "carmel_hip_exchange_info", "carmel_hip_exchange_measure", "carmel_hip_exchange_clear", "carmel_hip_set_layout_policy", "carmel_hip_set_matrix_fb",
     "carmel_hip_set_option", "carmel_hip_get_option", "carmel_hip_option_count", "carmel_hip_option_name",
+    "carmel_hip_decoder_create", "carmel_hip_decoder_set_weights", "carmel_hip_decode", "carmel_hip_decoder_get_paths",
+    "carmel_hip_decoder_last_ms", "carmel_hip_decoder_destroy",
 ]
 
 
@@ -217,6 +219,13 @@ def _load():
     lib.carmel_hip_forests_max_sample.restype = C.c_uint32
     lib.carmel_hip_forests_viterbi.argtypes = [vp, vp]
     lib.carmel_hip_forests_get_viterbi.argtypes = [vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32)]
+    lib.carmel_hip_decoder_create.argtypes = [C.POINTER(vp), C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp,
+                                              C.c_int]
+    lib.carmel_hip_decoder_set_weights.argtypes = [vp, vp]
+    lib.carmel_hip_decode.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
+    lib.carmel_hip_decoder_get_paths.argtypes = [vp, vp]
+    lib.carmel_hip_decoder_last_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.carmel_hip_decoder_destroy.argtypes = [vp]
     for s in SYMBOLS:  # a prototype for every entry point: without one ctypes passes Python ints as C int (64-bit seeds
         if getattr(lib, s).argtypes is None:  # and bare handles would be truncated)
             raise ImportError("carmel_amd: no ctypes prototype for %s" % s)

@@ -1,0 +1,506 @@
+// decode.hip — batch 1-best decoding (carmel -b -k 1: print_kbest / visit_kbest(1, ...), carmel.cc:378-398, fst.h:791) of many
+// lines against one (composed) transducer, on a tropical-semiring (max, +) trellis over (line position i, state q), f64 log
+// weights.  The reference composes each line with the machine and runs a reversed Dijkstra over the result (kbest.h:189,
+// graph.cc:148-208); here nothing is composed per line: a line only selects which arcs may advance a position.
+//
+// Line-independent preparation (carmel_hip_decoder_create, on the host, uploaded once):
+//   * the matched arcs (the matched side -- input, or output for side 1 -- is not *e*) in a CSR by symbol, each symbol's arcs
+//     sorted by (dst, arc id) and cut into one segment per destination state;
+//   * the epsilon arcs (matched side *e*) grouped into levels: level(q) = 1 + the largest level of an epsilon predecessor of q
+//     (0 without one), an arc filed under the level of its destination.  If the epsilon subgraph has a cycle there are no
+//     levels: the closure relaxes every epsilon arc in arc-id order, round after round, to a fixed point (at most |Q| rounds).
+//   Arcs of weight zero are dropped here: they are never taken.
+//
+// Per line (one wavefront = one workgroup of 64 lanes per line; lines launched longest first):
+//   d_0 = 0 at the start state (0), -inf elsewhere, closed over the epsilon arcs;
+//   d_{i+1}[q'] = max over arcs q -> q' labelled x_i of d_i[q] + w, then closed over the epsilon arcs;
+//   every (i, q') that is set or improved records the arc id in a back-pointer array of (n + 1) x |Q| u32.
+// The trellis adds in path order from the start (0 + w1 + w2 + ...): that is how it CHOOSES the path.  The weight it REPORTS is
+// the chosen path's arcs added from the end, w1 + (w2 + (... + (wn + 0))), summed by the walk that recovers the path: the
+// reference's best_w is the distance its reversed Dijkstra computes from the final state (kbest.h:203-213 dist[src], graph.cc
+// shortestPathTreeTo), and the summary line multiplies those.  (The two orders differ in the last bit for some lines; with path
+// order the cipher run's product misses the trace's last printed digit.)  A path printed with its weight (no -W) carries the
+// path-order sum (fst.h path_print: w *= arc.weight), which the front end adds up from the arcs.
+//
+// Tie rule (independent of lane count and scheduling): for a destination state the candidates are taken in arc-id order and
+// only a STRICTLY greater value replaces the one held, so the lowest arc id among equal candidates wins; the epsilon closure
+// that follows replaces a value only if it is strictly greater, so a matched arc beats an epsilon path of equal weight, and an
+// epsilon path of more levels beats one of fewer only if strictly better.  (The reference keeps the first strict improvement in
+// the pop order of its reversed Dijkstra; that rule is not replicated.)
+//
+// d_i and d_{i+1} are two rows of |Q| doubles: in LDS when 16 |Q| bytes fit 64 KiB (|Q| <= 4096), otherwise in a global scratch
+// buffer per line (the "global tier": correct, not fast).  The back-pointers are walked afterwards by one lane per line
+// (decode_walk_kernel), once to count a path's arcs and once to write them in path order.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <memory>
+#include <numeric>
+#include <string>
+#include <vector>
+#include "engine.hpp"
+
+namespace {
+constexpr uint32_t kNone = 0xffffffffu;
+constexpr int kLanes = 64;
+constexpr uint32_t kLdsStates = 4096;  // two rows of |Q| doubles in 64 KiB of LDS
+constexpr int kErrCycle = 1, kErrWalk = 2;
+
+struct DecodeTables {
+  uint32_t n_states, final_state, n_syms;  // n_syms: 1 + the largest matched symbol
+  const uint32_t* sym_seg;   // [n_syms + 1] -> segments
+  const uint32_t* seg_dst;   // [n_seg]
+  const uint32_t* seg_arc;   // [n_seg + 1] -> matched arcs
+  const uint32_t* m_src;     // matched arcs, by (symbol, dst, arc id)
+  const double* m_w;
+  const uint32_t* m_id;
+  uint32_t n_levels;         // epsilon levels (acyclic); 0 and eps_cyclic: one list in arc-id order
+  int eps_cyclic;
+  const uint32_t* lvl_ent;   // [n_levels + 1] -> entries (one destination state each)
+  const uint32_t* ent_dst;
+  const uint32_t* ent_arc;   // [n_ent + 1] -> epsilon arcs
+  const uint32_t* e_src;     // epsilon arcs, by (level, dst, arc id) -- or in arc-id order when cyclic
+  const uint32_t* e_dst;
+  const double* e_w;
+  const uint32_t* e_id;
+  uint32_t n_eps;
+};
+
+struct DecodeLines {
+  const uint64_t* off;     // chunk-local CSR of the lines' symbols
+  const uint32_t* sym;
+  const uint32_t* order;   // launch order: chunk-local line index of block b
+  const uint64_t* bp_off;  // [n + 1]: each line's (len + 1) x |Q| back-pointers
+  uint32_t* bp;
+  double* rows;            // global tier: 2 |Q| doubles per line (nullptr in the LDS tier)
+  double* best;            // [n]
+  int* err;
+};
+
+// close `row` (position i's values) over the epsilon arcs; `bpr` is that position's back-pointer row
+__device__ void eps_close(const DecodeTables& T, double* row, uint32_t* bpr, int lane, int* err) {
+  if (!T.eps_cyclic) {
+    for (uint32_t L = 0; L < T.n_levels; ++L) {
+      for (uint32_t e = T.lvl_ent[L] + lane; e < T.lvl_ent[L + 1]; e += kLanes) {
+        const uint32_t q = T.ent_dst[e];
+        double best = row[q];
+        uint32_t barc = kNone;
+        for (uint32_t k = T.ent_arc[e]; k < T.ent_arc[e + 1]; ++k) {
+          const double v = row[T.e_src[k]] + T.e_w[k];
+          if (v > best) {
+            best = v;
+            barc = T.e_id[k];
+          }
+        }
+        if (barc != kNone) {
+          row[q] = best;
+          bpr[q] = barc;
+        }
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  // a cyclic epsilon subgraph: Bellman-Ford in arc-id order on one lane, |Q| rounds at most; a change in round |Q| means a cycle
+  // that strictly improves a path (kbest.h:160-166 best_path_has_cycle)
+  if (lane == 0) {
+    bool changed = true;
+    for (uint32_t round = 0; changed && round <= T.n_states; ++round) {
+      changed = false;
+      for (uint32_t k = 0; k < T.n_eps; ++k) {
+        const double v = row[T.e_src[k]] + T.e_w[k];
+        const uint32_t q = T.e_dst[k];
+        if (v > row[q]) {
+          row[q] = v;
+          bpr[q] = T.e_id[k];
+          changed = true;
+        }
+      }
+      if (changed && round == T.n_states) atomicOr(err, kErrCycle);
+    }
+  }
+  __syncthreads();
+}
+
+template <bool kLds>
+__global__ void __launch_bounds__(kLanes) decode_trellis_kernel(DecodeTables T, DecodeLines D) {
+  extern __shared__ double lds_rows[];
+  const int lane = threadIdx.x;
+  const uint32_t line = D.order[blockIdx.x];
+  const uint32_t Q = T.n_states;
+  double* cur = kLds ? lds_rows : D.rows + (size_t)line * 2 * Q;
+  double* nxt = cur + Q;
+  const uint64_t s0 = D.off[line];
+  const uint32_t n = (uint32_t)(D.off[line + 1] - s0);
+  uint32_t* bp = D.bp + D.bp_off[line];
+  const double ninf = -std::numeric_limits<double>::infinity();
+  for (uint32_t q = lane; q < Q; q += kLanes) {
+    cur[q] = q == 0 ? 0.0 : ninf;
+    bp[q] = kNone;
+  }
+  __syncthreads();
+  eps_close(T, cur, bp, lane, D.err);
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t* bpn = bp + (size_t)(i + 1) * Q;
+    for (uint32_t q = lane; q < Q; q += kLanes) {
+      nxt[q] = ninf;
+      bpn[q] = kNone;
+    }
+    __syncthreads();
+    const uint32_t x = D.sym[s0 + i];
+    if (x < T.n_syms)  // (a symbol no arc matches leaves the row at -inf: no derivation)
+      for (uint32_t g = T.sym_seg[x] + lane; g < T.sym_seg[x + 1]; g += kLanes) {
+        double best = ninf;
+        uint32_t barc = kNone;
+        for (uint32_t k = T.seg_arc[g]; k < T.seg_arc[g + 1]; ++k) {
+          const double v = cur[T.m_src[k]] + T.m_w[k];
+          if (v > best) {
+            best = v;
+            barc = T.m_id[k];
+          }
+        }
+        if (barc != kNone) {
+          const uint32_t q = T.seg_dst[g];
+          nxt[q] = best;
+          bpn[q] = barc;
+        }
+      }
+    __syncthreads();
+    eps_close(T, nxt, bpn, lane, D.err);
+    double* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  if (lane == 0) D.best[line] = cur[T.final_state];
+}
+
+// one lane per line walks the back-pointers from (n, final) to (0, start): kWrite = false counts the path's arcs into len[line]
+// and replaces best[line] by the arcs' weights added from the end (the reference's k-best cost); kWrite = true writes the arcs
+// in path order at path[path_off[line] ..)
+template <bool kWrite>
+__global__ void decode_walk_kernel(uint32_t n_lines, uint32_t n_states, uint32_t final_state, uint64_t n_arcs, const uint64_t* off,
+                                   const uint64_t* bp_off, const uint32_t* bp, double* best, const uint32_t* a_src,
+                                   const uint8_t* a_eps, const double* a_w, uint32_t* len, const uint64_t* path_off, uint32_t* path,
+                                   int* err) {
+  const uint32_t line = blockIdx.x * blockDim.x + threadIdx.x;
+  if (line >= n_lines) return;
+  if (!(best[line] > -std::numeric_limits<double>::infinity())) {
+    if (!kWrite) len[line] = 0;
+    return;
+  }
+  uint32_t i = (uint32_t)(off[line + 1] - off[line]), q = final_state;
+  const uint32_t* b = bp + bp_off[line];
+  const uint64_t cap = (uint64_t)(i + 1) * n_states;  // no path of the trellis is longer
+  const uint32_t n_path = kWrite ? len[line] : 0;
+  uint32_t steps = 0;
+  double w = 0.0;
+  while (true) {
+    const uint32_t a = b[(size_t)i * n_states + q];
+    if (a == kNone) break;
+    if (a >= n_arcs || steps >= cap || (kWrite && steps >= n_path) || (!a_eps[a] && i == 0)) {
+      atomicOr(err, kErrWalk);
+      return;
+    }
+    ++steps;
+    if (kWrite) path[path_off[line] + n_path - steps] = a;
+    w = a_w[a] + w;
+    q = a_src[a];
+    if (!a_eps[a]) --i;
+  }
+  if (i != 0 || q != 0) atomicOr(err, kErrWalk);
+  if (!kWrite) {
+    len[line] = steps;
+    best[line] = w;
+  }
+}
+}  // namespace
+
+struct carmel_hip_decoder {
+  int device = 0;
+  int side = 0;
+  uint32_t n_states = 0, final_state = 0;
+  uint64_t n_arcs = 0;
+  std::vector<uint32_t> src, dst, msym;  // msym: the matched-side symbol of every arc
+  std::vector<double> logw;
+  bool eps_cyclic = false;
+  DevBuf<uint32_t> sym_seg, seg_dst, seg_arc, m_src, m_id, lvl_ent, ent_dst, ent_arc, e_src, e_dst, e_id, a_src;
+  DevBuf<double> m_w, e_w, a_w;
+  DevBuf<uint8_t> a_eps;
+  DecodeTables T;
+  std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
+  double last_ms = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~carmel_hip_decoder() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  int upload_tables();
+};
+
+int carmel_hip_decoder::upload_tables() {
+  const double ninf = -std::numeric_limits<double>::infinity();
+  const uint32_t Q = n_states;
+  std::vector<uint32_t> matched, eps;
+  uint32_t n_syms = 0;
+  for (uint64_t k = 0; k < n_arcs; ++k) {
+    if (!(logw[k] > ninf)) continue;  // zero-probability arcs are never taken
+    if (msym[k] == 0)
+      eps.push_back((uint32_t)k);
+    else {
+      matched.push_back((uint32_t)k);
+      n_syms = std::max(n_syms, msym[k] + 1);
+    }
+  }
+  // matched arcs: CSR by symbol, (symbol, dst, arc id) order, one segment per (symbol, dst)
+  std::stable_sort(matched.begin(), matched.end(), [&](uint32_t a, uint32_t b) {
+    return msym[a] != msym[b] ? msym[a] < msym[b] : dst[a] < dst[b];
+  });
+  std::vector<uint32_t> h_sym_seg(n_syms + 1, 0), h_seg_dst, h_seg_arc, h_msrc, h_mid;
+  std::vector<double> h_mw;
+  for (size_t j = 0; j < matched.size(); ++j) {
+    const uint32_t k = matched[j];
+    if (j == 0 || msym[k] != msym[matched[j - 1]] || dst[k] != dst[matched[j - 1]]) {
+      h_seg_dst.push_back(dst[k]);
+      h_seg_arc.push_back((uint32_t)j);
+      h_sym_seg[msym[k] + 1]++;
+    }
+    h_msrc.push_back(src[k]);
+    h_mw.push_back(logw[k]);
+    h_mid.push_back(k);
+  }
+  h_seg_arc.push_back((uint32_t)matched.size());
+  for (uint32_t x = 0; x < n_syms; ++x) h_sym_seg[x + 1] += h_sym_seg[x];
+  // epsilon arcs: levels of a topological order (Kahn), or one list in arc-id order if the subgraph is cyclic
+  std::vector<uint32_t> level(Q, 0), indeg(Q, 0);
+  std::vector<std::vector<uint32_t> > outs(Q);
+  for (uint32_t k : eps) {
+    outs[src[k]].push_back(k);
+    indeg[dst[k]]++;
+  }
+  std::vector<uint32_t> work;
+  for (uint32_t q = 0; q < Q; ++q)
+    if (!indeg[q]) work.push_back(q);
+  size_t seen = 0;
+  uint32_t n_levels = 0;
+  while (seen < work.size()) {
+    const uint32_t q = work[seen++];
+    for (uint32_t k : outs[q]) {
+      level[dst[k]] = std::max(level[dst[k]], level[q] + 1);
+      n_levels = std::max(n_levels, level[dst[k]]);
+      if (--indeg[dst[k]] == 0) work.push_back(dst[k]);
+    }
+  }
+  eps_cyclic = seen < Q;
+  std::vector<uint32_t> h_lvl_ent, h_ent_dst, h_ent_arc, h_esrc, h_edst, h_eid;
+  std::vector<double> h_ew;
+  if (eps_cyclic)
+    n_levels = 0;  // eps stays in arc-id order
+  else {
+    std::stable_sort(eps.begin(), eps.end(), [&](uint32_t a, uint32_t b) {
+      return level[dst[a]] != level[dst[b]] ? level[dst[a]] < level[dst[b]] : dst[a] < dst[b];
+    });
+    // levels 1 .. n_levels hold arcs (level 0 states have no epsilon predecessor)
+    h_lvl_ent.assign(n_levels + 1, 0);
+    for (size_t j = 0; j < eps.size(); ++j) {
+      const uint32_t k = eps[j];
+      if (j == 0 || dst[k] != dst[eps[j - 1]]) {
+        h_ent_dst.push_back(dst[k]);
+        h_ent_arc.push_back((uint32_t)j);
+        h_lvl_ent[level[dst[k]]]++;  // (level >= 1: counted into slot level - 1 + 1)
+      }
+    }
+    h_ent_arc.push_back((uint32_t)eps.size());
+    for (uint32_t L = 0; L < n_levels; ++L) h_lvl_ent[L + 1] += h_lvl_ent[L];
+  }
+  for (uint32_t k : eps) {
+    h_esrc.push_back(src[k]);
+    h_edst.push_back(dst[k]);
+    h_ew.push_back(logw[k]);
+    h_eid.push_back(k);
+  }
+  std::vector<uint8_t> h_aeps(n_arcs);
+  for (uint64_t k = 0; k < n_arcs; ++k) h_aeps[k] = msym[k] == 0;
+  hipStream_t s = stream;
+  HIPCHK(sym_seg.upload(h_sym_seg, s));
+  HIPCHK(seg_dst.upload(h_seg_dst, s));
+  HIPCHK(seg_arc.upload(h_seg_arc, s));
+  HIPCHK(m_src.upload(h_msrc, s));
+  HIPCHK(m_w.upload(h_mw, s));
+  HIPCHK(m_id.upload(h_mid, s));
+  HIPCHK(lvl_ent.upload(h_lvl_ent, s));
+  HIPCHK(ent_dst.upload(h_ent_dst, s));
+  HIPCHK(ent_arc.upload(h_ent_arc, s));
+  HIPCHK(e_src.upload(h_esrc, s));
+  HIPCHK(e_dst.upload(h_edst, s));
+  HIPCHK(e_w.upload(h_ew, s));
+  HIPCHK(e_id.upload(h_eid, s));
+  HIPCHK(a_src.upload(src, s));
+  HIPCHK(a_w.upload(logw, s));
+  HIPCHK(a_eps.upload(h_aeps, s));
+  HIPCHK(hipStreamSynchronize(s));
+  T = DecodeTables{Q, final_state, n_syms, sym_seg.p, seg_dst.p, seg_arc.p, m_src.p, m_w.p, m_id.p, n_levels, eps_cyclic ? 1 : 0,
+                   lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size()};
+  return CARMEL_HIP_OK;
+}
+
+extern "C" {
+
+int carmel_hip_decoder_create(carmel_hip_decoder** out, int device, uint32_t n_states, uint32_t final_state, uint64_t n_arcs,
+                              const uint32_t* src, const uint32_t* dst, const uint32_t* in_sym, const uint32_t* out_sym,
+                              const double* logw, int side) {
+  if (!out || !n_states || final_state >= n_states || (side != 0 && side != 1) || n_arcs >= kNone ||
+      (n_arcs && (!src || !dst || !in_sym || !out_sym || !logw)))
+    return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decoder_create: bad argument");
+  for (uint64_t k = 0; k < n_arcs; ++k)
+    if (src[k] >= n_states || dst[k] >= n_states) return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decoder_create: arc state out of range");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(CARMEL_HIP_ERR_HIP, "no HIP device: decoding has no CPU fallback");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<carmel_hip_decoder> d(new carmel_hip_decoder());
+  d->device = device;
+  d->side = side;
+  d->n_states = n_states;
+  d->final_state = final_state;
+  d->n_arcs = n_arcs;
+  d->src.assign(src, src + n_arcs);
+  d->dst.assign(dst, dst + n_arcs);
+  d->msym.assign(side ? out_sym : in_sym, (side ? out_sym : in_sym) + n_arcs);  // -r: the machine inverted
+  d->logw.assign(logw, logw + n_arcs);
+  HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+  HIPCHK(hipEventCreate(&d->ev0));
+  HIPCHK(hipEventCreate(&d->ev1));
+  const int rc = d->upload_tables();
+  if (rc) return rc;
+  *out = d.release();
+  return CARMEL_HIP_OK;
+}
+
+int carmel_hip_decoder_set_weights(carmel_hip_decoder* d, const double* logw) {
+  if (!d || (d->n_arcs && !logw)) return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decoder_set_weights: bad argument");
+  HIPCHK(hipSetDevice(d->device));
+  d->logw.assign(logw, logw + d->n_arcs);
+  return d->upload_tables();  // (which arcs have weight zero may have changed)
+}
+
+int carmel_hip_decode(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, double* best_logw,
+                      uint64_t* path_off) {
+  if (!d || !off || !best_logw || !path_off || (off[n_lines] && !sym))
+    return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decode: bad argument");
+  for (uint64_t l = 0; l < n_lines; ++l)
+    if (off[l + 1] < off[l] || off[l + 1] - off[l] >= kNone) return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decode: bad line offsets");
+  HIPCHK(hipSetDevice(d->device));
+  hipStream_t s = d->stream;
+  const uint32_t Q = d->n_states;
+  const bool lds = Q <= kLdsStates && !lib_opt_off("decode_lds");
+  // lines go in chunks, in line order, whose back-pointers (and global-tier rows) fit the budget ("decode_chunk_bytes", default
+  // 1 GiB; a single line larger than it goes alone)
+  uint64_t budget = 1ull << 30;
+  if (const char* v = lib_opt("decode_chunk_bytes")) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+  auto line_bytes = [&](uint64_t l) { return (off[l + 1] - off[l] + 1) * Q * 4ull + (lds ? 0 : 16ull * Q); };
+  d->paths.clear();
+  path_off[0] = 0;
+  float total_ms = 0;
+  DevBuf<uint64_t> d_off, d_bpoff, d_poff;
+  DevBuf<uint32_t> d_sym, d_order, d_bp, d_len, d_path;
+  DevBuf<double> d_rows, d_best;
+  DevBuf<int> d_err;
+  HIPCHK(d_err.alloc(1));
+  for (uint64_t lo = 0; lo < n_lines;) {
+    uint64_t hi = lo + 1, bytes = line_bytes(lo);
+    while (hi < n_lines && hi - lo < (1u << 24) && bytes + line_bytes(hi) <= budget) bytes += line_bytes(hi++);
+    const uint32_t n = (uint32_t)(hi - lo);
+    std::vector<uint64_t> h_off(n + 1), h_bpoff(n + 1);
+    for (uint32_t l = 0; l <= n; ++l) h_off[l] = off[lo + l] - off[lo];
+    h_bpoff[0] = 0;
+    for (uint32_t l = 0; l < n; ++l) h_bpoff[l + 1] = h_bpoff[l] + (h_off[l + 1] - h_off[l] + 1) * Q;
+    std::vector<uint32_t> order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t a, uint32_t b) { return h_off[a + 1] - h_off[a] > h_off[b + 1] - h_off[b]; });
+    HIPCHK(d_off.upload(h_off, s));
+    HIPCHK(d_bpoff.upload(h_bpoff, s));
+    const std::vector<uint32_t> h_sym(sym + off[lo], sym + off[hi]);  // (named: the copy is asynchronous)
+    HIPCHK(d_sym.upload(h_sym, s));
+    HIPCHK(d_order.upload(order, s));
+    HIPCHK(d_bp.alloc(h_bpoff[n]));
+    if (!lds) HIPCHK(d_rows.alloc((size_t)n * 2 * Q));
+    HIPCHK(d_best.alloc(n));
+    HIPCHK(d_len.alloc(n));
+    HIPCHK(hipMemsetAsync(d_err.p, 0, sizeof(int), s));
+    DecodeLines D{d_off.p, d_sym.p, d_order.p, d_bpoff.p, d_bp.p, lds ? nullptr : d_rows.p, d_best.p, d_err.p};
+    HIPCHK(hipEventRecord(d->ev0, s));
+    if (lds)
+      decode_trellis_kernel<true><<<n, kLanes, 16 * (size_t)Q, s>>>(d->T, D);
+    else
+      decode_trellis_kernel<false><<<n, kLanes, 0, s>>>(d->T, D);
+    HIPCHK(hipGetLastError());
+    const uint32_t wb = (n + 255) / 256;
+    decode_walk_kernel<false><<<wb, 256, 0, s>>>(n, Q, d->final_state, d->n_arcs, d_off.p, d_bpoff.p, d_bp.p, d_best.p, d->a_src.p,
+                                                 d->a_eps.p, d->a_w.p, d_len.p, nullptr, nullptr, d_err.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(d->ev1, s));
+    std::vector<uint32_t> len(n);
+    int err = 0;
+    HIPCHK(hipMemcpyAsync(best_logw + lo, d_best.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(len.data(), d_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&err, d_err.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+    total_ms += ms;
+    if (err & kErrCycle)  // kbest.h:160-166
+      return fail(CARMEL_HIP_ERR_UNSUPPORTED, "best_path_has_cycle: the best path has a cycle (an epsilon cycle of weight > 1)");
+    if (err) return fail(CARMEL_HIP_ERR_STATE, "carmel_hip_decode: inconsistent back-pointers");
+    std::vector<uint64_t> h_poff(n + 1, 0);
+    for (uint32_t l = 0; l < n; ++l) h_poff[l + 1] = h_poff[l] + len[l];
+    for (uint32_t l = 0; l < n; ++l) path_off[lo + l + 1] = path_off[lo + l] + len[l];
+    if (h_poff[n]) {
+      HIPCHK(d_poff.upload(h_poff, s));
+      HIPCHK(d_path.alloc(h_poff[n]));
+      HIPCHK(hipEventRecord(d->ev0, s));
+      decode_walk_kernel<true><<<wb, 256, 0, s>>>(n, Q, d->final_state, d->n_arcs, d_off.p, d_bpoff.p, d_bp.p, d_best.p, d->a_src.p,
+                                                  d->a_eps.p, d->a_w.p, d_len.p, d_poff.p, d_path.p, d_err.p);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(d->ev1, s));
+      const size_t at = d->paths.size();
+      d->paths.resize(at + h_poff[n]);
+      HIPCHK(hipMemcpyAsync(d->paths.data() + at, d_path.p, h_poff[n] * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(&err, d_err.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+      total_ms += ms;
+      if (err) return fail(CARMEL_HIP_ERR_STATE, "carmel_hip_decode: inconsistent back-pointers");
+    }
+    lo = hi;
+  }
+  d->last_ms = total_ms;
+  return CARMEL_HIP_OK;
+}
+
+int carmel_hip_decoder_get_paths(carmel_hip_decoder* d, uint32_t* arcs) {
+  if (!d || (!arcs && !d->paths.empty())) return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decoder_get_paths: bad argument");
+  if (!d->paths.empty()) std::memcpy(arcs, d->paths.data(), d->paths.size() * sizeof(uint32_t));
+  return CARMEL_HIP_OK;
+}
+
+int carmel_hip_decoder_last_ms(carmel_hip_decoder* d, double* kernel_ms) {
+  if (!d || !kernel_ms) return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decoder_last_ms: bad argument");
+  *kernel_ms = d->last_ms;
+  return CARMEL_HIP_OK;
+}
+
+int carmel_hip_decoder_destroy(carmel_hip_decoder* d) {
+  if (d) {
+    (void)hipSetDevice(d->device);
+    delete d;
+  }
+  return CARMEL_HIP_OK;
+}
+
+}  // extern "C"

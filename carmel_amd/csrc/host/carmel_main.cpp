@@ -124,6 +124,7 @@ struct Options {
   long crp_iters = -1, burnin = 0;
   double high_temp = 1, low_temp = 1;  // --high-temp / --low-temp (carmel.cc:289-290)
   unsigned long long seed = 1;
+  long kpaths = 0;  // -k n (carmel.cc:1021): best paths per line; only n = 1 with -b / -i (batch decoding, decode_batch)
   std::vector<const char*> files;
 };
 
@@ -331,6 +332,7 @@ static Options parse_args(int argc, char** argv) {
           case 'o':  // learning rate growth factor of over-relaxed EM (carmel.cc:940-943)
             o.rate_growth = std::max(1.0, std::atof(value()));
             break;
+          case 'k': o.kpaths = std::atol(value()); break;
           case '+':  // pseudo-Dirichlet-process normalisation exp(digamma(alpha + w)) (carmel.cc:1009-1013)
             o.plus_alpha = std::atof(value());
             o.plus_alpha_set = true;
@@ -338,8 +340,8 @@ static Options parse_args(int argc, char** argv) {
           default:
             // switches without a value that this front end implements; everything else carmel knows (k-best, generation,
             // projection, pruning, OpenFst, ...) is outside the training path
-            // (O I Q W E @: WFST::path_print, fst.h:60-160 -- how --print-to writes the sampled paths)
-            if (!std::strchr("tUujnlqdKmHJZDB2?:caShOIQWE@1", a[j]))
+            // (O I Q W E @: WFST::path_print, fst.h:60-160 -- how --print-to writes the sampled paths; b s r i: batch decoding)
+            if (!std::strchr("tUujnlqdKmHJZDB2?:caShOIQWE@1bsri", a[j]))
               throw UsageError(std::string("switch -") + a[j] + " is not implemented by the GPU training front end");
             break;
         }
@@ -360,6 +362,140 @@ static Options parse_args(int argc, char** argv) {
 // the reference's iteration control then behaves the same way
 static inline double ppxper(double ln_p, double n) {
   return ln_p == -std::numeric_limits<double>::infinity() ? ln_p : -ln_p / n;
+}
+
+// ---- batch 1-best decoding: carmel -b -k 1 (carmel.cc:1266-1384, report_batch :355-376, print_kbest :378-398) ----
+// The reference composes every line with the cascade and searches the result; here the cascade is composed ONCE and every
+// line is decoded against it on the GPU (carmel_hip_decode, csrc/decode.hip), all lines in one call.  A path prints as
+// WFST::path_print does (fst.h:60-160) in its -I / -O / -@ forms (-Q -W -E apply); the arc form needs the state names of a
+// per-line composition, which is never built, and is refused before this is reached.
+static int decode_batch(const Options& o, Transducer& M, const std::string& text, int ws, bool quiet, int device) {
+  const bool side_out = o.flags[(unsigned)'r'];
+  std::vector<std::string> lines;
+  for (size_t p = 0; p < text.size();) {  // getline: an empty line is the empty string (Carmel 6.9, carmel.cc:1269-1270)
+    size_t e = text.find('\n', p);
+    if (e == std::string::npos) e = text.size();
+    lines.push_back(text.substr(p, e - p));
+    p = e + 1;
+    if (!o.flags[(unsigned)'b']) break;  // -i without -b: one line (carmel.cc:1380)
+  }
+  if (lines.empty()) {
+    std::cerr << "No lines of input provided.\n";
+    return 0;
+  }
+  // WFST::WFST(const char*) (wfstio.cc:152-172): the line's symbols; a symbol the machine never saw gets an id no arc carries
+  std::vector<uint64_t> off(1, 0);
+  std::vector<uint32_t> sym;
+  double n_symbols = 0;  // carmel.cc:1277-1283: the sum of the lines' lengths
+  for (size_t l = 0; l < lines.size(); ++l) {
+    std::string& ln = lines[l];
+    if (!ln.empty() && ln.back() == '\r') ln.pop_back();  // (getString drops a DOS CR)
+    std::vector<uint32_t> ids;
+    M.symbols_of_line(ln, side_out, ids);
+    const SymbolTable& tab = side_out ? M.out_syms : M.in_syms;
+    for (uint32_t id : ids)
+      if (std::isdigit((unsigned char)tab.names[id][0])) {
+        std::cerr << "Couldn't handle input line: " << ln << "\n";
+        return -3;
+      }
+    sym.insert(sym.end(), ids.begin(), ids.end());
+    off.push_back(sym.size());
+    n_symbols += (double)ids.size();
+  }
+  std::vector<uint32_t> src, dst, in, out, group;
+  std::vector<double> logw;
+  M.flatten(src, dst, in, out, logw, group);
+  carmel_hip_decoder* d = 0;
+  hip_check(carmel_hip_decoder_create(&d, device, (uint32_t)M.states.size(), M.final_state, logw.size(), src.data(), dst.data(),
+                                      in.data(), out.data(), logw.data(), side_out ? 1 : 0),
+            "carmel_hip_decoder_create");
+  struct Guard {
+    carmel_hip_decoder* d;
+    ~Guard() { carmel_hip_decoder_destroy(d); }
+  } guard{d};
+  const size_t n = lines.size();
+  std::vector<double> best(n);
+  std::vector<uint64_t> path_off(n + 1);
+  const auto t0 = std::chrono::steady_clock::now();
+  hip_check(carmel_hip_decode(d, n, off.data(), sym.data(), best.data(), path_off.data()), "carmel_hip_decode");
+  std::vector<uint32_t> path(std::max<uint64_t>(path_off[n], 1));
+  hip_check(carmel_hip_decoder_get_paths(d, path.data()), "carmel_hip_decoder_get_paths");
+  if (std::getenv("CARMEL_TIMING")) {
+    double kms = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    std::cerr << "timing: decode " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+              << " s (kernels " << kms * 1e-3 << " s)\n";
+  }
+  std::vector<const HArc*> arc_of;
+  for (auto& st : M.states)
+    for (auto& a : st) arc_of.push_back(&a);
+  const bool fO = o.flags[(unsigned)'O'], fQ = o.flags[(unsigned)'Q'], fAT = o.flags[(unsigned)'@'], fW = o.flags[(unsigned)'W'],
+             fE = o.flags[(unsigned)'E'];
+  auto name = [&](bool output, uint32_t id) -> std::string {
+    const std::string& x = output ? M.out_syms.names[id] : M.in_syms.names[id];
+    return (!fQ || x.size() < 2 || x[0] != '"' || x[x.size() - 1] != '"') ? x : x.substr(1, x.size() - 2);  // outWithoutQuotes
+  };
+  size_t n_0prob = 0;
+  double n_prob = 0, prod_viterbi = 0;
+  std::string buf;
+  for (size_t l = 0; l < n; ++l) {
+    if (!quiet) std::cerr << "Input line " << l + 1 << ": " << lines[l] << "\n";
+    buf.clear();
+    if (!(best[l] > kNegInf)) {  // print_kbest's fill line
+      ++n_0prob;
+      if (!(fW || fAT)) buf += '0';
+      buf += '\n';
+      std::cout << buf;
+      continue;
+    }
+    ++n_prob;
+    prod_viterbi += best[l];  // non0_viterbi_prob: prod_viterbi *= best_w (the search's cost, carmel_hip_decode), in line order
+    bool first = true;
+    auto sp = [&]() {
+      if (!first) buf += ' ';
+      first = false;
+    };
+    std::vector<uint32_t> outs;
+    for (uint64_t k = path_off[l]; k < path_off[l + 1]; ++k) {
+      const HArc& a = *arc_of[path[k]];
+      if (fAT) {
+        if (a.out != 0) outs.push_back(a.out);
+        if (a.in != 0) {
+          sp();
+          buf += M.in_syms.names[a.in];
+        }
+      } else {
+        const uint32_t id = fO ? a.out : a.in;
+        if (!(fE && id == 0)) {
+          sp();
+          buf += name(fO, id);
+        }
+      }
+    }
+    if (fAT) {
+      buf += '\n';
+      for (size_t j = 0; j < outs.size(); ++j) buf += (j ? " " : "") + M.out_syms.names[outs[j]];
+    } else if (!fW) {  // path_print's own weight: the arcs multiplied in path order (fst.h path_print::arc)
+      double lw_path = 0.0;
+      for (uint64_t k = path_off[l]; k < path_off[l + 1]; ++k) lw_path += arc_of[path[k]]->logw;
+      sp();
+      buf += format_weight(lw_path, ws);
+    }
+    buf += '\n';
+    std::cout << buf;
+  }
+  std::cout << std::flush;
+  // report_batch (carmel.cc:355-376) with log_ppx (:306-318) and Weight::print_ppx (weight.h:321-329)
+  if (n_0prob)
+    std::cerr << "No derivations found for " << n_0prob << " of " << n << " inputs.\n";
+  else
+    std::cerr << "Derivations found for all " << n << " inputs.\n";
+  std::cerr << "Viterbi (best path) product of probs=" << format_weight(prod_viterbi, ws) << ", probability=" << base2(prod_viterbi);
+  if (n_symbols) std::cerr << " per-input-symbol-perplexity(N=" << n_symbols << ")=" << base2(ppxper(prod_viterbi, n_symbols));
+  if (n_prob) std::cerr << " per-line-perplexity(N=" << n_prob << ")=" << base2(ppxper(prod_viterbi, n_prob));
+  if (n_0prob) std::cerr << ", excluding " << n_0prob << " 0 probabilities (i.e. real ppx is infinite).";
+  std::cerr << std::endl;
+  return 0;
 }
 
 struct CorpusStats {  // training_corpus counters over the pairs that have a derivation (train.h:151-168)
@@ -399,8 +535,34 @@ static int run(int argc, char** argv) {
                  "options: --train-cascade --normby= --priors= --digamma= --random-set --disk-cache-derivations= --matrix-fb; "
                  "the sampler: --crp[=N] --burnin= --crp-restarts= --print-every= --print-from= --print-to= --print-counts-from= "
                  "--print-counts-to= --print-norms-from= --print-norms-to= --width= ... ; several GPUs: --gpus=N --exchange=; "
+                 "batch 1-best decoding: -b -i -s -r -k 1 with -I / -O / -@ (-Q -W -E); "
                  "the full list and what each replaces: INTEGRATION.md\n";
     return 0;
+  }
+  // ---- batch decoding (-b / -i with -k 1): what is not implemented is refused here, before any device call ----
+  const bool decoding = o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0;
+  if (decoding) {
+    if (o.kpaths > 1) throw UsageError("-k n with n > 1 (k-best paths) is not implemented; -k 1 with -b or -i is");
+    if (o.kpaths < 1) throw UsageError("-b / -i without -k 1 (printing each line's composition) is not implemented");
+    if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i'])
+      throw UsageError("-k without -b or -i (k-best paths of the whole cascade) is not implemented");
+    if (with_pairs) throw UsageError("-k with -t / --train-cascade / -S is not implemented");
+    if (!o.flags[(unsigned)'I'] && !o.flags[(unsigned)'O'] && !o.flags[(unsigned)'@'])
+      throw UsageError("-k without -I, -O or -@ (the arc path form: state names of a per-line composition) is not implemented");
+  } else if (o.flags[(unsigned)'s'] || o.flags[(unsigned)'r'])
+    throw UsageError("-s / -r apply to batch decoding (-b or -i with -k 1)");
+  std::string line_text;
+  if (decoding) {  // the line stream: stdin with -s, else the first file (the last with -r) (carmel.cc:1099-1115, 1186-1191)
+    if (o.flags[(unsigned)'s']) {
+      std::stringstream ss;
+      ss << std::cin.rdbuf();
+      line_text = ss.str();
+    } else {
+      if (o.files.size() < 2) throw UsageError("-b / -i without -s need a file of lines and a transducer");
+      const size_t at = o.flags[(unsigned)'r'] ? o.files.size() - 1 : 0;
+      line_text = slurp(o.files[at]);
+      o.files.erase(o.files.begin() + at);
+    }
   }
   if (o.files.empty() || (with_pairs && o.files.size() < 2)) {
     std::cerr << "usage: carmel -t [--train-cascade] [-M n] [-e d] [-X r] [-f w] [-U] [-u|-j] [-HJZD] [-F out] "
@@ -634,6 +796,7 @@ static int run(int argc, char** argv) {
     }
     if (!quiet) std::cerr << std::endl;
   }
+  if (decoding) return decode_batch(o, *result, line_text, wstyle, quiet, o.gpu);
   if (!with_pairs) {  // plain `carmel a b ...`: print the (reduced) composition — no GPU involved
     const int ws = wstyle;
     if (o.flags[(unsigned)'c'])

@@ -521,6 +521,33 @@ int carmel_hip_composition_export(carmel_hip_composition* c, uint64_t* state_off
                                   double* arc_logw, uint32_t* arc_ka, uint32_t* arc_kb);
 int carmel_hip_composition_free(carmel_hip_composition* c);
 
+/* ---- batch 1-best decoding (carmel -b -k 1; csrc/decode.hip) ----
+ * A decoder holds one (composed) transducer, independent of any trainer: the arc arrays carmel_hip_create takes (state 0 the
+ * start), so a library user can decode with the weights carmel_hip_get_arc_weights returns.  `side` 0: a line is a string of
+ * INPUT symbols (carmel -i / -b, the line composed on the left); 1: of OUTPUT symbols (-r, composed on the right) -- the
+ * machine is inverted once here.  There is no CPU fallback: without a device creation fails (CARMEL_HIP_ERR_HIP).
+ * Replaces: the per-line composition of carmel.cc:1266-1360 followed by print_kbest(1, result) (carmel.cc:378-398), i.e.
+ * WFST::visit_kbest(1, ...) (fst.h:791 -> kbest.h:189, graph.cc:148-208). */
+typedef struct carmel_hip_decoder carmel_hip_decoder;
+int carmel_hip_decoder_create(carmel_hip_decoder** out, int device, uint32_t n_states, uint32_t final_state, uint64_t n_arcs,
+                              const uint32_t* src, const uint32_t* dst, const uint32_t* in_sym, const uint32_t* out_sym,
+                              const double* logw, int side);
+/* new weights for the same arcs (arc-id order); replaces assigning weights to the machine before decoding (WFST::assignWeights) */
+int carmel_hip_decoder_set_weights(carmel_hip_decoder* d, const double* logw);
+/* Replaces: the -b line loop with print_kbest (carmel.cc:1266-1384).  Line l is sym[off[l] .. off[l + 1]) (symbol ids of the
+ * matched side's alphabet; an id no arc carries means no derivation).  best_logw[l] = ln of the best path's weight as the
+ * reference's k-best search reports it (print_kbest's best_w: the arcs' logs added from the END, w1 + (w2 + (... + wn)), the
+ * distance of kbest.h:203-213), -inf = no derivation; the path is chosen by path-order sums; path_off (n_lines
+ * + 1 entries) delimits each line's path in carmel_hip_decoder_get_paths.  Ties: the lowest arc id.  An epsilon cycle
+ * that strictly improves a path fails with best_path_has_cycle (kbest.h:160-166), CARMEL_HIP_ERR_UNSUPPORTED. */
+int carmel_hip_decode(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, double* best_logw,
+                      uint64_t* path_off);
+/* the last decode's paths: path_off[n_lines] arc ids, each line's in path order (wfst_paths_printer's arcs, fst.h:60-160) */
+int carmel_hip_decoder_get_paths(carmel_hip_decoder* d, uint32_t* arcs);
+/* the last decode's kernel time (HIP events around the trellis and walk kernels, summed over chunks) */
+int carmel_hip_decoder_last_ms(carmel_hip_decoder* d, double* kernel_ms);
+int carmel_hip_decoder_destroy(carmel_hip_decoder* d);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;

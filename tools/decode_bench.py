@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""Batch 1-best decoding on the MI355X (csrc/decode.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
+the output side as in `carmel -qbsriWIEk 1`) over tagging.data.noe repeated to about --lines lines, then the front end's
+end-to-end time for the tutorial's three decode commands.  Prints one JSON object.
+
+    python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst]
+
+The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
+on the weights); the cluster and cipher commands use their committed trained members."""
+import argparse
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+G = os.path.join(ROOT, "tests", "golden")
+CLI = os.path.join(ROOT, "carmel_amd", "bin", "carmel")
+
+
+def composed(members):
+    """the composed machine as `carmel -HJ` prints it, read back through the oracle's composition (exact weights)"""
+    from oracle import binding as ob
+    oc = ob.OracleCascade([open(m).read() for m in members], remember=False)
+    return oc, oc.composed().arrays()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lines", type=int, default=100000)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--fst", default=os.path.join(G, "tagging.fst"))
+    a = ap.parse_args()
+    from carmel_amd.decode import Decoder
+    from carmel_amd.model import Wfst
+    from decode_ref import golden_file
+    tmp = tempfile.mkdtemp()
+    gf = lambda name: golden_file(G, name, tmp)  # (the larger fixtures are committed compressed)
+    data = [l for l in open(os.path.join(G, "tagging.data")).read().split("\n") if l.split()]
+    oc, w = composed([gf("tagging.fsa.trained.noe"), a.fst])
+    c = oc.corpus("".join("\n%s\n" % l for l in data)).arrays()
+    base = [c["out_sym"][int(c["out_off"][k]):int(c["out_off"][k + 1])] for k in range(len(data))]
+    lines = (base * (a.lines // len(base) + 1))[:a.lines]
+    W = Wfst(w["n_states"], w["final"], w["src"], w["dst"], w["isym"], w["osym"], w["logw"])
+    d = Decoder(W, side=1)
+    d.decode(lines[:1000])  # warm-up (code objects, allocations)
+    ms, wall = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        best, paths = d.decode(lines)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(d.last_ms())
+    d.close()
+    n_pos = int(sum(len(x) for x in lines))
+    # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
+    per_sym = np.bincount(w["osym"][w["logw"] > -np.inf].astype(np.int64))
+    relax = int(sum(int(per_sym[x].sum()) if len(x) else 0 for x in [np.asarray(l, np.int64) for l in lines]))
+    kms = float(np.median(ms))
+    res = {"workload": "tagging decode (-r), %d lines, %d positions" % (len(lines), n_pos),
+           "machine": {"states": int(w["n_states"]), "arcs": int(len(w["src"]))},
+           "kernel_ms": kms, "kernel_ms_all": ms, "call_ms": float(np.median(wall)),
+           "lines_per_s": len(lines) / (kms * 1e-3), "relaxations_per_s": relax / (kms * 1e-3), "relaxations": relax,
+           "no_derivation": int(np.isneginf(best).sum())}
+    cmds = {"cluster": ("cluster.data.noe", ["cat.fsa.trained.noe", "spellout.fst.trained"]),
+            "tagging": ("tagging.data", ["tagging.fsa.trained.noe", a.fst]),
+            "cipher": ("cipher.data", ["cipher.wfsa.noe", "cipher.fst.trained"])}
+    e2e = {}
+    for name, (data_file, members) in cmds.items():
+        text = "".join(l + "\n" for l in open(gf(data_file)).read().split("\n") if l.split())
+        t0 = time.perf_counter()
+        p = subprocess.run([CLI, "-qbsriWIEk", "1"] + [gf(m) if not os.path.isabs(m) else m for m in members], input=text,
+                           capture_output=True,
+                           text=True, env=dict(os.environ, CARMEL_TIMING="1"), timeout=600)
+        e2e[name] = {"rc": p.returncode, "seconds": time.perf_counter() - t0,
+                     "timing": [l for l in p.stderr.split("\n") if l.startswith("timing: decode")]}
+    res["end_to_end"] = e2e
+    shutil.rmtree(tmp)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
