@@ -800,12 +800,14 @@ int mstep_args(carmel_hip_trainer* t, int use_counts, int save_old, MstepArgs& M
   M.big_groups = t->big_groups.p;
   M.n_groups = t->n_norm_groups;
   M.n_big = t->big_groups.n;
-  if (t->max_partial.n != MSTEP_PARTIALS + t->big_groups.n) {
-    HIPCHK(t->max_partial.alloc(MSTEP_PARTIALS + t->big_groups.n));
-    HIPCHK(hipMemsetAsync(t->max_partial.p, 0, t->max_partial.bytes(), s));  // once: mstep_max_final_kernel clears what it reads
+  if (t->max_partial.n != MSTEP_PARTIALS + t->big_groups.n + MSTEP_WIDE_TICKETS) {  // (the ticket counters of mstep_wide_kernel)
+    HIPCHK(t->max_partial.alloc(MSTEP_PARTIALS + t->big_groups.n + MSTEP_WIDE_TICKETS));
+    // once: mstep_max_final_kernel clears what it reads, mstep_wide_kernel's last workgroup the slots and the ticket
+    HIPCHK(hipMemsetAsync(t->max_partial.p, 0, t->max_partial.bytes(), s));
     t->mstep_stream_work = true;  // (an M-step launched on another stream must wait for this: exchange.cpp, the direct form)
   }
   M.max_partial = t->max_partial.p;
+  M.ticket = t->max_partial.p + MSTEP_PARTIALS + t->big_groups.n;
   M.gscale = t->gscale.p;
   M.tie_of = t->n_ties ? t->tie_of.p : nullptr;
   M.tie_tab = t->tie_tab.p;
@@ -828,7 +830,14 @@ static int run_mstep(carmel_hip_trainer* t, int use_counts, int save_old) {
   MstepArgs M;
   int rc = mstep_args(t, use_counts, save_old, M);
   if (rc) return rc;
-  HIPCHK(launch_mstep(M, use_counts, t->stream));
+  // the one-pass window M-step of a whole model runs in its batched form, which also delivers the result (one launch instead
+  // of two); mstep_wide: "0" = mstep_window_kernel + mstep_max_final_kernel (A/B), N >= 8 = a grid of at most N workgroups
+  // instead of what the device holds at once
+  const int wide = lib_opt("mstep_wide") ? atoi(lib_opt("mstep_wide")) : 1;
+  if (wide && mstep_wide_can(M, use_counts))
+    HIPCHK(launch_mstep_wide(M, use_counts, wide >= 8 ? (uint32_t)wide : 0u, t->stream));
+  else
+    HIPCHK(launch_mstep(M, use_counts, t->stream));
   return CARMEL_HIP_OK;
 }
 

@@ -139,6 +139,9 @@ struct TransArgs {
                            // chain of 500 dependent loads: 0.22 ms on the tagging lexicon's per-tag groups)
 #define MSTEP_PARTIALS 2048
 #define MSTEP_MAX_RANGES 17
+#define MSTEP_WIDE_SLOTS 512      // mstep_wide_kernel folds its workgroups' maxima into the first so many entries of max_partial
+#define MSTEP_WIDE_SHARDS 32       // its workgroups arrive at so many ticket counters, the last of each at the root counter
+#define MSTEP_WIDE_TICKETS (16 * (MSTEP_WIDE_SHARDS + 1))  // entries behind max_partial: the root, then a shard every 128 bytes
 struct MstepArgs {
   double* logw;             // parameters (ln), updated in place
   const double* lw_src;     // mstep_window_kernel: where the ln weights of the tile AND its halo are read -- `logw` itself
@@ -195,6 +198,10 @@ struct MstepArgs {
   // scope) when box != null: the host spins on the sequence number instead of a copy command and a stream synchronisation
   unsigned long long* box = nullptr;
   unsigned long long box_seq = 0;
+  // mstep_wide_kernel (mstep_wide.hip): the arrival counters of its workgroups (MSTEP_WIDE_TICKETS entries), allocated and
+  // zeroed with max_partial; whoever draws the last ticket folds the partial slots, publishes the result as above and puts
+  // the counter back to zero
+  unsigned long long* ticket = nullptr;
 };
 
 // fused: the XC form of the backward pass (LaneArgs::xc_* set; the groups lie on LANE_FUSED_TILE boundaries)
@@ -230,6 +237,12 @@ hipError_t launch_count_reduce(const ReduceArgs& R, hipStream_t stream);
 hipError_t launch_fill(double* p, double v, uint64_t n, hipStream_t s);
 hipError_t launch_add(double* dst, const double* src, uint64_t n, hipStream_t s);  // dst += src
 hipError_t launch_mstep(const MstepArgs& M, int use_counts, hipStream_t s);
+// mstep_wide.hip: the whole-model one-pass window M-step in batched form, result and mailbox included (ONE launch; the same
+// bits as mstep_window_kernel + mstep_max_final_kernel).  mstep_wide_can: this launch is one it handles (window path, no
+// ties, no digamma, no block ranges, tables aligned for its wide loads); grid_cap: workgroups at most, 0 = as many as the
+// device holds at once
+bool mstep_wide_can(const MstepArgs& M, int use_counts);
+hipError_t launch_mstep_wide(const MstepArgs& M, int use_counts, uint32_t grid_cap, hipStream_t s);
 hipError_t launch_overrelax(double* logw, const double* old_logw, double* em_logw, const uint32_t* group, double rate,
                             uint64_t n, hipStream_t s);
 hipError_t launch_max_change(const double* logw, const double* old_logw, const uint32_t* group,

@@ -10,6 +10,7 @@ pids=()
 for f in kernels.hip tile_sweep.hip engine.cpp engine_unrolled.cpp compose.hip matrix_fb.hip lattice_gpu.hip comm.cpp exchange.cpp dense.hip unrolled.hip; do
   /opt/rocm/bin/hipcc $CXX $HIPFLAGS "$@" -c $f -o $OUT/${f%.*}.o & pids+=($!)
 done
+/opt/rocm/bin/hipcc $CXX $HIPFLAGS -mllvm -disable-machine-licm "$@" -c mstep_wide.hip -o $OUT/mstep_wide.o & pids+=($!)  # (Makefile: WIDEFLAGS)
 for f in gibbs_exact.hip gibbs.hip forest_exact.hip forest.hip; do
   /opt/rocm/bin/hipcc $CXX $HIPFLAGS -ffp-contract=off "$@" -c $f -o $OUT/${f%.*}.o & pids+=($!)
 done
