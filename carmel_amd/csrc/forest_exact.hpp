@@ -1,5 +1,5 @@
 // forest_exact.hpp — the reference's forest sampler chain (forest-em --crp without --crp-parallel) as ONE persistent
-// kernel per sweep (forest_exact.hip); arguments as forest.hip's carmel_hip_forests_gibbs fills them.
+// kernel per sweep (forest_exact.hip); arguments as forest_gibbs.cpp's carmel_hip_forests_gibbs fills them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -17,7 +17,7 @@ const char* const kKeys[] = {
     "tile_sweep_kernel", "mailbox", "poison", "lane_trace", "exchange_sparse", "mstep_wide",
     // one-tape cascades (engine_unrolled.cpp, unrolled.cpp)
     "dense", "unrolled", "unrolled_ragged",
-    // the samplers (gibbs.hip, forest.hip)
+    // the samplers (gibbs.hip, forest_gibbs.cpp)
     "gibbs_chains", "gibbs_own_cap", "gibbs_workgroup", "gibbs_clk", "gibbs_reg", "gibbs_lane", "forest_sweep", "forest_ldswalk", "forest_multi",
     "forest_nohash", "forest_trace", "forest_exact_host", "forest_exact_clk", "forest_logdomain", "forest_gcol", "forest_gather",
     // batch decoding (decode.hip): "0" puts the trellis rows in global memory for any |Q|; the back-pointer budget of a chunk of lines
