@@ -31,6 +31,7 @@
 // d_i and d_{i+1} are two rows of |Q| doubles: in LDS when 16 |Q| bytes fit 64 KiB (|Q| <= 4096), otherwise in a global scratch
 // buffer per line (the "global tier": correct, not fast).  The back-pointers are walked afterwards by one lane per line
 // (decode_walk_kernel), once to count a path's arcs and once to write them in path order.
+// The tables, the handle and the constants are in decode.hpp, shared with the k-best decoder (decode_kbest.hip).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -41,34 +42,10 @@
 #include <numeric>
 #include <string>
 #include <vector>
+#include "decode.hpp"
 #include "engine.hpp"
 
 namespace {
-constexpr uint32_t kNone = 0xffffffffu;
-constexpr int kLanes = 64;
-constexpr uint32_t kLdsStates = 4096;  // two rows of |Q| doubles in 64 KiB of LDS
-constexpr int kErrCycle = 1, kErrWalk = 2;
-
-struct DecodeTables {
-  uint32_t n_states, final_state, n_syms;  // n_syms: 1 + the largest matched symbol
-  const uint32_t* sym_seg;   // [n_syms + 1] -> segments
-  const uint32_t* seg_dst;   // [n_seg]
-  const uint32_t* seg_arc;   // [n_seg + 1] -> matched arcs
-  const uint32_t* m_src;     // matched arcs, by (symbol, dst, arc id)
-  const double* m_w;
-  const uint32_t* m_id;
-  uint32_t n_levels;         // epsilon levels (acyclic); 0 and eps_cyclic: one list in arc-id order
-  int eps_cyclic;
-  const uint32_t* lvl_ent;   // [n_levels + 1] -> entries (one destination state each)
-  const uint32_t* ent_dst;
-  const uint32_t* ent_arc;   // [n_ent + 1] -> epsilon arcs
-  const uint32_t* e_src;     // epsilon arcs, by (level, dst, arc id) -- or in arc-id order when cyclic
-  const uint32_t* e_dst;
-  const double* e_w;
-  const uint32_t* e_id;
-  uint32_t n_eps;
-};
-
 struct DecodeLines {
   const uint64_t* off;     // chunk-local CSR of the lines' symbols
   const uint32_t* sym;
@@ -218,30 +195,6 @@ __global__ void decode_walk_kernel(uint32_t n_lines, uint32_t n_states, uint32_t
 }
 }  // namespace
 
-struct carmel_hip_decoder {
-  int device = 0;
-  int side = 0;
-  uint32_t n_states = 0, final_state = 0;
-  uint64_t n_arcs = 0;
-  std::vector<uint32_t> src, dst, msym;  // msym: the matched-side symbol of every arc
-  std::vector<double> logw;
-  bool eps_cyclic = false;
-  DevBuf<uint32_t> sym_seg, seg_dst, seg_arc, m_src, m_id, lvl_ent, ent_dst, ent_arc, e_src, e_dst, e_id, a_src;
-  DevBuf<double> m_w, e_w, a_w;
-  DevBuf<uint8_t> a_eps;
-  DecodeTables T;
-  std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
-  double last_ms = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~carmel_hip_decoder() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  int upload_tables();
-};
-
 int carmel_hip_decoder::upload_tables() {
   const double ninf = -std::numeric_limits<double>::infinity();
   const uint32_t Q = n_states;
@@ -325,6 +278,8 @@ int carmel_hip_decoder::upload_tables() {
   }
   std::vector<uint8_t> h_aeps(n_arcs);
   for (uint64_t k = 0; k < n_arcs; ++k) h_aeps[k] = msym[k] == 0;
+  std::vector<uint8_t> h_epsin(Q, 0);
+  for (uint32_t k : eps) h_epsin[dst[k]] = 1;
   hipStream_t s = stream;
   HIPCHK(sym_seg.upload(h_sym_seg, s));
   HIPCHK(seg_dst.upload(h_seg_dst, s));
@@ -342,6 +297,7 @@ int carmel_hip_decoder::upload_tables() {
   HIPCHK(a_src.upload(src, s));
   HIPCHK(a_w.upload(logw, s));
   HIPCHK(a_eps.upload(h_aeps, s));
+  HIPCHK(eps_in.upload(h_epsin, s));
   HIPCHK(hipStreamSynchronize(s));
   T = DecodeTables{Q, final_state, n_syms, sym_seg.p, seg_dst.p, seg_arc.p, m_src.p, m_w.p, m_id.p, n_levels, eps_cyclic ? 1 : 0,
                    lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size()};

@@ -125,6 +125,8 @@ struct Options {
   double high_temp = 1, low_temp = 1;  // --high-temp / --low-temp (carmel.cc:289-290)
   unsigned long long seed = 1;
   long kpaths = 0;  // -k n (carmel.cc:1021): best paths per line; only n = 1 with -b / -i (batch decoding, decode_batch)
+  long kbest = 0;   // --kbest=N: N best paths per line (print_kbest(N, ...), carmel.cc:379-397), where -k 1 is accepted
+  bool have_kbest = false;
   std::vector<const char*> files;
 };
 
@@ -235,6 +237,10 @@ static Options parse_args(int argc, char** argv) {
         o.init_from_p0 = true;
       else if (k == "gpu-compose")
         o.gpu_compose = true;
+      else if (k == "kbest") {  // not a carmel option: -k n with n > 1 (carmel_hip_decode_kbest)
+        o.kbest = std::atol(v.c_str());
+        o.have_kbest = true;
+      }
       else if (k == "disk-cache-derivations") {
         // carmel.cc:243-246, fst.h:1057-1076: the reference spills its derivation cache to disk when it outgrows memory (and
         // without -? rebuilds every pair's derivations in every iteration, cached_derivs.h:60-101).  Here: when the lattices of
@@ -369,6 +375,8 @@ static inline double ppxper(double ln_p, double n) {
 // line is decoded against it on the GPU (carmel_hip_decode, csrc/decode.hip), all lines in one call.  A path prints as
 // WFST::path_print does (fst.h:60-160) in its -I / -O / -@ forms (-Q -W -E apply); the arc form needs the state names of a
 // per-line composition, which is never built, and is refused before this is reached.
+// --kbest=N prints, for every line, its N best derivations best first and then print_kbest's fill lines up to N
+// (carmel_hip_decode_kbest, csrc/decode_kbest.hip); the summary multiplies each line's first path, as with -k 1.
 static int decode_batch(const Options& o, Transducer& M, const std::string& text, int ws, bool quiet, int device) {
   const bool side_out = o.flags[(unsigned)'r'];
   std::vector<std::string> lines;
@@ -414,12 +422,37 @@ static int decode_batch(const Options& o, Transducer& M, const std::string& text
     ~Guard() { carmel_hip_decoder_destroy(d); }
   } guard{d};
   const size_t n = lines.size();
-  std::vector<double> best(n);
-  std::vector<uint64_t> path_off(n + 1);
+  const size_t kbest = o.have_kbest ? (size_t)o.kbest : 1;  // output lines per input line
+  // line l's paths are line_paths[l] .. line_paths[l + 1]; path p has the search's cost best[p] and the arcs
+  // path[path_off[p] .. path_off[p + 1])
+  std::vector<double> best;
+  std::vector<uint64_t> path_off, line_paths(n + 1, 0);
+  std::vector<uint32_t> path;
   const auto t0 = std::chrono::steady_clock::now();
-  hip_check(carmel_hip_decode(d, n, off.data(), sym.data(), best.data(), path_off.data()), "carmel_hip_decode");
-  std::vector<uint32_t> path(std::max<uint64_t>(path_off[n], 1));
-  hip_check(carmel_hip_decoder_get_paths(d, path.data()), "carmel_hip_decoder_get_paths");
+  if (o.have_kbest) {
+    hip_check(carmel_hip_decode_kbest(d, (uint32_t)kbest, n, off.data(), sym.data(), line_paths.data()), "carmel_hip_decode_kbest");
+    uint64_t n_paths = 0, n_path_arcs = 0;
+    hip_check(carmel_hip_decoder_kbest_size(d, &n_paths, &n_path_arcs), "carmel_hip_decoder_kbest_size");
+    best.resize(std::max<uint64_t>(n_paths, 1));
+    path_off.resize(n_paths + 1);
+    path.resize(std::max<uint64_t>(n_path_arcs, 1));
+    hip_check(carmel_hip_decoder_get_kbest(d, best.data(), path_off.data(), path.data()), "carmel_hip_decoder_get_kbest");
+  } else {
+    std::vector<double> best1(n);
+    std::vector<uint64_t> off1(n + 1);
+    hip_check(carmel_hip_decode(d, n, off.data(), sym.data(), best1.data(), off1.data()), "carmel_hip_decode");
+    path.resize(std::max<uint64_t>(off1[n], 1));
+    hip_check(carmel_hip_decoder_get_paths(d, path.data()), "carmel_hip_decoder_get_paths");
+    path_off.assign(1, 0);
+    for (size_t l = 0; l < n; ++l) {  // (a line without a derivation has no path)
+      const bool has = best1[l] > kNegInf;
+      if (has) {
+        best.push_back(best1[l]);
+        path_off.push_back(off1[l + 1]);
+      }
+      line_paths[l + 1] = line_paths[l] + (has ? 1 : 0);
+    }
+  }
   if (std::getenv("CARMEL_TIMING")) {
     double kms = 0;
     carmel_hip_decoder_last_ms(d, &kms);
@@ -441,47 +474,51 @@ static int decode_batch(const Options& o, Transducer& M, const std::string& text
   for (size_t l = 0; l < n; ++l) {
     if (!quiet) std::cerr << "Input line " << l + 1 << ": " << lines[l] << "\n";
     buf.clear();
-    if (!(best[l] > kNegInf)) {  // print_kbest's fill line
+    const uint64_t p0 = line_paths[l], p1 = line_paths[l + 1];
+    if (p0 == p1)
       ++n_0prob;
-      if (!(fW || fAT)) buf += '0';
-      buf += '\n';
-      std::cout << buf;
-      continue;
+    else {
+      ++n_prob;
+      prod_viterbi += best[p0];  // non0_viterbi_prob: prod_viterbi *= best_w (the search's cost, carmel_hip_decode), in line order
     }
-    ++n_prob;
-    prod_viterbi += best[l];  // non0_viterbi_prob: prod_viterbi *= best_w (the search's cost, carmel_hip_decode), in line order
-    bool first = true;
-    auto sp = [&]() {
-      if (!first) buf += ' ';
-      first = false;
-    };
-    std::vector<uint32_t> outs;
-    for (uint64_t k = path_off[l]; k < path_off[l + 1]; ++k) {
-      const HArc& a = *arc_of[path[k]];
-      if (fAT) {
-        if (a.out != 0) outs.push_back(a.out);
-        if (a.in != 0) {
-          sp();
-          buf += M.in_syms.names[a.in];
-        }
-      } else {
-        const uint32_t id = fO ? a.out : a.in;
-        if (!(fE && id == 0)) {
-          sp();
-          buf += name(fO, id);
+    for (uint64_t p = p0; p < p1; ++p) {
+      bool first = true;
+      auto sp = [&]() {
+        if (!first) buf += ' ';
+        first = false;
+      };
+      std::vector<uint32_t> outs;
+      for (uint64_t k = path_off[p]; k < path_off[p + 1]; ++k) {
+        const HArc& a = *arc_of[path[k]];
+        if (fAT) {
+          if (a.out != 0) outs.push_back(a.out);
+          if (a.in != 0) {
+            sp();
+            buf += M.in_syms.names[a.in];
+          }
+        } else {
+          const uint32_t id = fO ? a.out : a.in;
+          if (!(fE && id == 0)) {
+            sp();
+            buf += name(fO, id);
+          }
         }
       }
-    }
-    if (fAT) {
+      if (fAT) {
+        buf += '\n';
+        for (size_t j = 0; j < outs.size(); ++j) buf += (j ? " " : "") + M.out_syms.names[outs[j]];
+      } else if (!fW) {  // path_print's own weight: the arcs multiplied in path order (fst.h path_print::arc)
+        double lw_path = 0.0;
+        for (uint64_t k = path_off[p]; k < path_off[p + 1]; ++k) lw_path += arc_of[path[k]]->logw;
+        sp();
+        buf += format_weight(lw_path, ws);
+      }
       buf += '\n';
-      for (size_t j = 0; j < outs.size(); ++j) buf += (j ? " " : "") + M.out_syms.names[outs[j]];
-    } else if (!fW) {  // path_print's own weight: the arcs multiplied in path order (fst.h path_print::arc)
-      double lw_path = 0.0;
-      for (uint64_t k = path_off[l]; k < path_off[l + 1]; ++k) lw_path += arc_of[path[k]]->logw;
-      sp();
-      buf += format_weight(lw_path, ws);
     }
-    buf += '\n';
+    for (uint64_t f = p1 - p0; f < kbest; ++f) {  // print_kbest's fill lines
+      if (!(fW || fAT)) buf += '0';
+      buf += '\n';
+    }
     std::cout << buf;
   }
   std::cout << std::flush;
@@ -536,14 +573,21 @@ static int run(int argc, char** argv) {
                  "the sampler: --crp[=N] --burnin= --crp-restarts= --print-every= --print-from= --print-to= --print-counts-from= "
                  "--print-counts-to= --print-norms-from= --print-norms-to= --width= ... ; several GPUs: --gpus=N --exchange=; "
                  "batch 1-best decoding: -b -i -s -r -k 1 with -I / -O / -@ (-Q -W -E); "
+                 "k-best decoding: --kbest=N (N <= 1024) in place of -k 1; "
                  "the full list and what each replaces: INTEGRATION.md\n";
     return 0;
   }
   // ---- batch decoding (-b / -i with -k 1): what is not implemented is refused here, before any device call ----
-  const bool decoding = o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0;
+  const bool decoding = o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0 || o.have_kbest;
   if (decoding) {
-    if (o.kpaths > 1) throw UsageError("-k n with n > 1 (k-best paths) is not implemented; -k 1 with -b or -i is");
-    if (o.kpaths < 1) throw UsageError("-b / -i without -k 1 (printing each line's composition) is not implemented");
+    if (o.have_kbest) {
+      if (o.kbest < 1 || o.kbest > 1024) throw UsageError("--kbest=N needs 1 <= N <= 1024");
+      if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.kbest) throw UsageError("--kbest=N with -k m: m must be 1 or N");
+    } else {
+      if (o.kpaths > 1)
+        throw UsageError("-k n with n > 1 (k-best paths) is not implemented; -k 1 with -b or -i is; use --kbest=n");
+      if (o.kpaths < 1) throw UsageError("-b / -i without -k 1 (printing each line's composition) is not implemented");
+    }
     if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i'])
       throw UsageError("-k without -b or -i (k-best paths of the whole cascade) is not implemented");
     if (with_pairs) throw UsageError("-k with -t / --train-cascade / -S is not implemented");

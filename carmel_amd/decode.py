@@ -1,10 +1,14 @@
-"""Batch 1-best decoding on the GPU (carmel -b -k 1; include/carmel_hip.h carmel_hip_decoder_*, csrc/decode.hip).
+"""Batch 1-best and k-best decoding on the GPU (carmel -b -k n; include/carmel_hip.h carmel_hip_decoder_*, csrc/decode.hip and
+csrc/decode_kbest.hip).
 
     d = Decoder(wfst, side=0)          # side 0: lines are input strings; 1: output strings (carmel -r)
     best, paths = d.decode(lines)      # lines: sequences of symbol ids of that side's alphabet
+    weights, kpaths = d.decode_kbest(lines, k)
     d.set_weights(logw); d.close()
 
-best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order."""
+best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
+weights[l] holds the reported ln weights of line l's min(k, number of derivations) best derivations, best first, and kpaths[l]
+their arc ids; rank 0 is decode's path."""
 import ctypes as C
 
 import numpy as np
@@ -37,6 +41,32 @@ class Decoder(object):
         check(lib.carmel_hip_decoder_get_paths(self._h, ptr(arcs)), "carmel_hip_decoder_get_paths")
         paths = [arcs[int(path_off[l]):int(path_off[l + 1])].copy() for l in range(len(lines))]
         return best, paths
+
+    def decode_kbest_raw(self, lines, k):
+        """-> (line_paths, logw, path_off, arcs): the arrays of carmel_hip_decode_kbest / carmel_hip_decoder_get_kbest"""
+        lines = [np.asarray(x, dtype=np.uint32) for x in lines]
+        off = u64(np.concatenate([[0], np.cumsum([len(x) for x in lines], dtype=np.uint64)]))
+        sym = u32(np.concatenate(lines)) if off[-1] else np.zeros(1, np.uint32)
+        line_paths = np.zeros(len(lines) + 1, np.uint64)
+        check(lib.carmel_hip_decode_kbest(self._h, int(k), len(lines), ptr(off), ptr(sym), ptr(line_paths)),
+              "carmel_hip_decode_kbest")
+        n_paths, n_arcs = C.c_uint64(), C.c_uint64()
+        check(lib.carmel_hip_decoder_kbest_size(self._h, C.byref(n_paths), C.byref(n_arcs)), "carmel_hip_decoder_kbest_size")
+        assert n_paths.value == int(line_paths[-1])
+        logw = np.zeros(max(n_paths.value, 1))
+        path_off = np.zeros(n_paths.value + 1, np.uint64)
+        arcs = np.zeros(max(n_arcs.value, 1), np.uint32)
+        check(lib.carmel_hip_decoder_get_kbest(self._h, ptr(logw), ptr(path_off), ptr(arcs)), "carmel_hip_decoder_get_kbest")
+        return line_paths, logw[:n_paths.value], path_off, arcs[:n_arcs.value]
+
+    def decode_kbest(self, lines, k):
+        line_paths, logw, path_off, arcs = self.decode_kbest_raw(lines, k)
+        weights, paths = [], []
+        for l in range(len(lines)):
+            a, b = int(line_paths[l]), int(line_paths[l + 1])
+            weights.append(logw[a:b].copy())
+            paths.append([arcs[int(path_off[p]):int(path_off[p + 1])].copy() for p in range(a, b)])
+        return weights, paths
 
     def last_ms(self):
         ms = C.c_double()

@@ -544,9 +544,30 @@ int carmel_hip_decode(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* o
                       uint64_t* path_off);
 /* the last decode's paths: path_off[n_lines] arc ids, each line's in path order (wfst_paths_printer's arcs, fst.h:60-160) */
 int carmel_hip_decoder_get_paths(carmel_hip_decoder* d, uint32_t* arcs);
-/* the last decode's kernel time (HIP events around the trellis and walk kernels, summed over chunks) */
+/* the last decode's (1-best or k-best) kernel time (HIP events around the trellis and walk kernels, summed over chunks) */
 int carmel_hip_decoder_last_ms(carmel_hip_decoder* d, double* kernel_ms);
 int carmel_hip_decoder_destroy(carmel_hip_decoder* d);
+
+/* ---- batch k-best decoding (carmel -b -k n; csrc/decode_kbest.hip) ----
+ * Replaces: the -b line loop with print_kbest(k, result) (carmel.cc:379-397), i.e. WFST::visit_kbest(k, ...) (fst.h:791,
+ * kbest.h).  Lines as for carmel_hip_decode.  Line l gets its min(k, number of derivations) best derivations -- paths
+ * line_paths[l] .. line_paths[l + 1] of carmel_hip_decoder_get_kbest (line_paths: n_lines + 1 entries) -- greatest value first.
+ * Two derivations differ if their arc-id sequences differ; equal printed strings are not merged (the reference prints such
+ * duplicates too).  A derivation's VALUE, by which the paths are chosen and ordered, is its arcs' logs added in path order from
+ * the start; candidates of equal value are ordered matched arc before epsilon arc, then lower arc id, then lower predecessor
+ * rank, on every machine, so rank 0 of a line is the very path carmel_hip_decode returns.  The weight REPORTED for
+ * a path is, as there, its arcs' logs added from the END (fst.h:791 visit_kbest's cost, kbest.h:203-213): a line's reported
+ * weights may therefore fail to be monotone in the last bit.  1 <= k <= 1024, else CARMEL_HIP_ERR_ARG.  If the matched side's
+ * epsilon arcs have a cycle: k = 1 behaves as carmel_hip_decode (best_path_has_cycle included); k > 1 fails with
+ * CARMEL_HIP_ERR_UNSUPPORTED, naming the epsilon cycle, and nothing is written.  May alternate with carmel_hip_decode on one
+ * handle; carmel_hip_decoder_last_ms covers these kernels too. */
+int carmel_hip_decode_kbest(carmel_hip_decoder* d, uint32_t k, uint64_t n_lines, const uint64_t* off, const uint32_t* sym,
+                            uint64_t* line_paths);
+/* the last k-best decode's sizes (fst.h:791 / carmel.cc:379-397: what print_kbest would visit): paths, and arcs of all paths */
+int carmel_hip_decoder_kbest_size(carmel_hip_decoder* d, uint64_t* n_paths, uint64_t* n_arcs);
+/* the last k-best decode's paths (fst.h:791 / carmel.cc:379-397): path p has reported weight path_logw[p] and the arc ids
+ * arcs[path_off[p] .. path_off[p + 1]) in path order; path_off has n_paths + 1 entries */
+int carmel_hip_decoder_get_kbest(carmel_hip_decoder* d, double* path_logw, uint64_t* path_off, uint32_t* arcs);
 
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Batch 1-best decoding on the MI355X (csrc/decode.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
+"""Batch 1-best and k-best decoding on the MI355X (csrc/decode.hip, csrc/decode_kbest.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
 the output side as in `carmel -qbsriWIEk 1`) over tagging.data.noe repeated to about --lines lines, then the front end's
-end-to-end time for the tutorial's three decode commands.  Prints one JSON object.
+end-to-end time for the tutorial's three decode commands.  Every --kbest K adds the same lines through carmel_hip_decode_kbest
+with that K ("kbest": kernel and call time, paths returned, and for K = 1 the ratio to the 1-best kernels' time of this run).
+Prints one JSON object.
 
-    python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst]
+    python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...]
 
 The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
 on the weights); the cluster and cipher commands use their committed trained members."""
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--lines", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fst", default=os.path.join(G, "tagging.fst"))
+    ap.add_argument("--kbest", type=int, action="append", default=[], metavar="K")
     a = ap.parse_args()
     from carmel_amd.decode import Decoder
     from carmel_amd.model import Wfst
@@ -57,6 +60,19 @@ def main():
         best, paths = d.decode(lines)
         wall.append((time.perf_counter() - t0) * 1e3)
         ms.append(d.last_ms())
+    kbest = {}
+    for K in a.kbest:
+        d.decode_kbest_raw(lines[:1000], K)
+        kms_k, wall_k = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            line_paths, logw, path_off, arcs = d.decode_kbest_raw(lines, K)
+            wall_k.append((time.perf_counter() - t0) * 1e3)
+            kms_k.append(d.last_ms())
+        kbest[str(K)] = {"kernel_ms": float(np.median(kms_k)), "kernel_ms_all": kms_k, "call_ms": float(np.median(wall_k)),
+                         "paths": int(len(logw)), "path_arcs": int(len(arcs)),
+                         "rank0_equals_1best": bool(np.array_equal(logw[line_paths[:-1][np.diff(line_paths) > 0].astype(np.int64)],
+                                                                   best[~np.isneginf(best)]))}
     d.close()
     n_pos = int(sum(len(x) for x in lines))
     # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
@@ -68,6 +84,10 @@ def main():
            "kernel_ms": kms, "kernel_ms_all": ms, "call_ms": float(np.median(wall)),
            "lines_per_s": len(lines) / (kms * 1e-3), "relaxations_per_s": relax / (kms * 1e-3), "relaxations": relax,
            "no_derivation": int(np.isneginf(best).sum())}
+    if kbest:
+        res["kbest"] = kbest
+        for K, v in kbest.items():
+            v["kernel_ms_over_1best"] = v["kernel_ms"] / kms
     cmds = {"cluster": ("cluster.data.noe", ["cat.fsa.trained.noe", "spellout.fst.trained"]),
             "tagging": ("tagging.data", ["tagging.fsa.trained.noe", a.fst]),
             "cipher": ("cipher.data", ["cipher.wfsa.noe", "cipher.fst.trained"])}
