@@ -1,0 +1,206 @@
+// carmel_decode.cpp — batch 1-best decoding: carmel -b -k 1 (carmel.cc:1266-1384, report_batch :355-376, print_kbest :378-398).
+// The reference composes every line with the cascade and searches the result; here the cascade is composed ONCE and every
+// line is decoded against it on the GPU (carmel_hip_decode, csrc/decode.hip), all lines in one call.  A path prints as
+// WFST::path_print does (fst.h:60-160) in its -I / -O / -@ forms (-Q -W -E apply); the arc form needs the state names of a
+// per-line composition, which is never built, and is refused before this is reached.
+// --kbest=N prints, for every line, its N best derivations best first and then print_kbest's fill lines up to N
+// (carmel_hip_decode_kbest, csrc/decode_kbest.hip); the summary multiplies each line's first path, as with -k 1.
+#include <cctype>
+#include "carmel_cli.hpp"
+using namespace carmel_host;
+
+namespace {
+struct Batch {  // the lines of one call and what the four steps below make of them
+  const Options& o;
+  Transducer& M;
+  const int ws;
+  std::vector<std::string> lines;
+  // WFST::WFST(const char*) (wfstio.cc:152-172): the line's symbols; a symbol the machine never saw gets an id no arc carries
+  std::vector<uint64_t> off = std::vector<uint64_t>(1, 0);
+  std::vector<uint32_t> sym;
+  double n_symbols = 0;  // carmel.cc:1277-1283: the sum of the lines' lengths
+  // line l's paths are line_paths[l] .. line_paths[l + 1]; path p has the search's cost best[p] and the arcs
+  // path[path_off[p] .. path_off[p + 1])
+  std::vector<double> best;
+  std::vector<uint64_t> path_off, line_paths;
+  std::vector<uint32_t> path;
+  std::vector<const HArc*> arc_of;
+  size_t n_0prob = 0;
+  double n_prob = 0, prod_viterbi = 0;
+
+  int read_lines(const std::string& text, bool side_out);
+  void decode(carmel_hip_decoder* d, size_t kbest);
+  void format_path(uint64_t p, std::string& buf) const;
+  void print_paths(size_t kbest, bool quiet);
+  void report() const;
+};
+
+int Batch::read_lines(const std::string& text, bool side_out) {
+  for (size_t p = 0; p < text.size();) {  // getline: an empty line is the empty string (Carmel 6.9, carmel.cc:1269-1270)
+    size_t e = text.find('\n', p);
+    if (e == std::string::npos) e = text.size();
+    lines.push_back(text.substr(p, e - p));
+    p = e + 1;
+    if (!o.flags[(unsigned)'b']) break;  // -i without -b: one line (carmel.cc:1380)
+  }
+  for (size_t l = 0; l < lines.size(); ++l) {
+    std::string& ln = lines[l];
+    if (!ln.empty() && ln.back() == '\r') ln.pop_back();  // (getString drops a DOS CR)
+    std::vector<uint32_t> ids;
+    M.symbols_of_line(ln, side_out, ids);
+    const SymbolTable& tab = side_out ? M.out_syms : M.in_syms;
+    for (uint32_t id : ids)
+      if (std::isdigit((unsigned char)tab.names[id][0])) {
+        std::cerr << "Couldn't handle input line: " << ln << "\n";
+        return -3;
+      }
+    sym.insert(sym.end(), ids.begin(), ids.end());
+    off.push_back(sym.size());
+    n_symbols += (double)ids.size();
+  }
+  return 0;
+}
+
+void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
+  const size_t n = lines.size();
+  line_paths.assign(n + 1, 0);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (o.have_kbest) {
+    hip_check(carmel_hip_decode_kbest(d, (uint32_t)kbest, n, off.data(), sym.data(), line_paths.data()), "carmel_hip_decode_kbest");
+    uint64_t n_paths = 0, n_path_arcs = 0;
+    hip_check(carmel_hip_decoder_kbest_size(d, &n_paths, &n_path_arcs), "carmel_hip_decoder_kbest_size");
+    best.resize(std::max<uint64_t>(n_paths, 1));
+    path_off.resize(n_paths + 1);
+    path.resize(std::max<uint64_t>(n_path_arcs, 1));
+    hip_check(carmel_hip_decoder_get_kbest(d, best.data(), path_off.data(), path.data()), "carmel_hip_decoder_get_kbest");
+  } else {
+    std::vector<double> best1(n);
+    std::vector<uint64_t> off1(n + 1);
+    hip_check(carmel_hip_decode(d, n, off.data(), sym.data(), best1.data(), off1.data()), "carmel_hip_decode");
+    path.resize(std::max<uint64_t>(off1[n], 1));
+    hip_check(carmel_hip_decoder_get_paths(d, path.data()), "carmel_hip_decoder_get_paths");
+    path_off.assign(1, 0);
+    for (size_t l = 0; l < n; ++l) {  // (a line without a derivation has no path)
+      const bool has = best1[l] > kNegInf;
+      if (has) {
+        best.push_back(best1[l]);
+        path_off.push_back(off1[l + 1]);
+      }
+      line_paths[l + 1] = line_paths[l] + (has ? 1 : 0);
+    }
+  }
+  if (timing_on()) {
+    double kms = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    std::cerr << "timing: decode " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+              << " s (kernels " << kms * 1e-3 << " s)\n";
+  }
+}
+
+// one path of a line into buf, as path_print writes it
+void Batch::format_path(uint64_t p, std::string& buf) const {
+  const bool fO = o.flags[(unsigned)'O'], fQ = o.flags[(unsigned)'Q'], fAT = o.flags[(unsigned)'@'], fW = o.flags[(unsigned)'W'],
+             fE = o.flags[(unsigned)'E'];
+  auto name = [&](bool output, uint32_t id) -> std::string {
+    const std::string& x = output ? M.out_syms.names[id] : M.in_syms.names[id];
+    return (!fQ || x.size() < 2 || x[0] != '"' || x[x.size() - 1] != '"') ? x : x.substr(1, x.size() - 2);  // outWithoutQuotes
+  };
+  bool first = true;
+  auto sp = [&]() {
+    if (!first) buf += ' ';
+    first = false;
+  };
+  std::vector<uint32_t> outs;
+  for (uint64_t k = path_off[p]; k < path_off[p + 1]; ++k) {
+    const HArc& a = *arc_of[path[k]];
+    if (fAT) {
+      if (a.out != 0) outs.push_back(a.out);
+      if (a.in != 0) {
+        sp();
+        buf += M.in_syms.names[a.in];
+      }
+    } else {
+      const uint32_t id = fO ? a.out : a.in;
+      if (!(fE && id == 0)) {
+        sp();
+        buf += name(fO, id);
+      }
+    }
+  }
+  if (fAT) {
+    buf += '\n';
+    for (size_t j = 0; j < outs.size(); ++j) buf += (j ? " " : "") + M.out_syms.names[outs[j]];
+  } else if (!fW) {  // path_print's own weight: the arcs multiplied in path order (fst.h path_print::arc)
+    double lw_path = 0.0;
+    for (uint64_t k = path_off[p]; k < path_off[p + 1]; ++k) lw_path += arc_of[path[k]]->logw;
+    sp();
+    buf += format_weight(lw_path, ws);
+  }
+  buf += '\n';
+}
+
+void Batch::print_paths(size_t kbest, bool quiet) {
+  for (auto& st : M.states)
+    for (auto& a : st) arc_of.push_back(&a);
+  const bool fAT = o.flags[(unsigned)'@'], fW = o.flags[(unsigned)'W'];
+  std::string buf;
+  for (size_t l = 0; l < lines.size(); ++l) {
+    if (!quiet) std::cerr << "Input line " << l + 1 << ": " << lines[l] << "\n";
+    buf.clear();
+    const uint64_t p0 = line_paths[l], p1 = line_paths[l + 1];
+    if (p0 == p1)
+      ++n_0prob;
+    else {
+      ++n_prob;
+      prod_viterbi += best[p0];  // non0_viterbi_prob: prod_viterbi *= best_w (the search's cost, carmel_hip_decode), in line order
+    }
+    for (uint64_t p = p0; p < p1; ++p) format_path(p, buf);
+    for (uint64_t f = p1 - p0; f < kbest; ++f) {  // print_kbest's fill lines
+      if (!(fW || fAT)) buf += '0';
+      buf += '\n';
+    }
+    std::cout << buf;
+  }
+  std::cout << std::flush;
+}
+
+// report_batch (carmel.cc:355-376) with log_ppx (:306-318) and Weight::print_ppx (weight.h:321-329)
+void Batch::report() const {
+  const size_t n = lines.size();
+  if (n_0prob)
+    std::cerr << "No derivations found for " << n_0prob << " of " << n << " inputs.\n";
+  else
+    std::cerr << "Derivations found for all " << n << " inputs.\n";
+  std::cerr << "Viterbi (best path) product of probs=" << format_weight(prod_viterbi, ws) << ", probability=" << base2(prod_viterbi);
+  if (n_symbols) std::cerr << " per-input-symbol-perplexity(N=" << n_symbols << ")=" << base2(ppxper(prod_viterbi, n_symbols));
+  if (n_prob) std::cerr << " per-line-perplexity(N=" << n_prob << ")=" << base2(ppxper(prod_viterbi, n_prob));
+  if (n_0prob) std::cerr << ", excluding " << n_0prob << " 0 probabilities (i.e. real ppx is infinite).";
+  std::cerr << std::endl;
+}
+}  // namespace
+
+int decode_batch(const Options& o, Transducer& M, const std::string& text, int ws, bool quiet, int device) {
+  const bool side_out = o.flags[(unsigned)'r'];
+  Batch b{o, M, ws};
+  if (int rc = b.read_lines(text, side_out)) return rc;
+  if (b.lines.empty()) {
+    std::cerr << "No lines of input provided.\n";
+    return 0;
+  }
+  std::vector<uint32_t> src, dst, in, out, group;
+  std::vector<double> logw;
+  M.flatten(src, dst, in, out, logw, group);
+  carmel_hip_decoder* d = 0;
+  hip_check(carmel_hip_decoder_create(&d, device, (uint32_t)M.states.size(), M.final_state, logw.size(), src.data(), dst.data(),
+                                      in.data(), out.data(), logw.data(), side_out ? 1 : 0),
+            "carmel_hip_decoder_create");
+  struct Guard {
+    carmel_hip_decoder* d;
+    ~Guard() { carmel_hip_decoder_destroy(d); }
+  } guard{d};
+  const size_t kbest = o.have_kbest ? (size_t)o.kbest : 1;  // output lines per input line
+  b.decode(d, kbest);
+  b.print_paths(kbest, quiet);
+  b.report();
+  return 0;
+}

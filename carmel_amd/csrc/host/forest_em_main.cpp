@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/carmel_hip.h"
+#include "cli_util.hpp"
 #include "env_options.hpp"
 #include "forest_text.hpp"
 
@@ -113,47 +114,6 @@ void spit(const std::string& fn, const std::string& text) {
     if (!of) throw std::runtime_error("can't create " + fn);
     of << text;
   }
-}
-void check(int rc, const char* what) {
-  if (rc != CARMEL_HIP_OK) throw std::runtime_error(std::string(what) + ": " + carmel_hip_last_error());
-}
-
-// print_width (graehl/shared/print_width.hpp:98-130): a number in at most `width` characters
-void print_width(std::ostream& os, double d, int width0) {
-  if (width0 >= 20 || d == 0. || width0 <= 0) {
-    os << d;
-    return;
-  }
-  const std::ios::fmtflags f = os.flags();
-  const std::streamsize pr = os.precision();
-  int width = width0;
-  double pa = d;
-  if (d < 0) {
-    pa = -d;
-    --width;
-  }
-  auto sig_for_exp = [](int w, int e) {
-    const int r = w - (e < 100 ? 2 : 3) - 3;
-    return r > 0 ? r : 0;
-  };
-  const double wholes = std::log10(pa * (1 + 1e-8));
-  if (wholes <= width && d == (double)(int)d)
-    os << d;
-  else if (pa < 1) {
-    const int a = (int)-wholes, need = 2 + a;
-    if (need >= width)
-      os << std::scientific << std::setprecision(sig_for_exp(width, a) - 1) << d;
-    else
-      os << std::setprecision(width - 2 - a) << d;
-  } else {
-    const int a = (int)wholes, need = 1 + a;
-    if (need > width)
-      os << std::scientific << std::setprecision(sig_for_exp(width, a) - 1) << d;
-    else
-      os << std::fixed << std::setprecision(need + 1 < width ? width - need - 1 : 0) << d;
-  }
-  os.flags(f);
-  os.precision(pr);
 }
 
 Opts parse_args(int argc, char** argv) {
@@ -340,7 +300,7 @@ int main(int argc, char** argv) {
     log << fs.n_forests() << " forests, " << fs.label.size() << " nodes, " << max_rule << " parameters in "
         << group_off.size() - 1 << " normalization groups.\n";
     carmel_hip_forests* F = nullptr;
-    check(carmel_hip_forests_create(&F, o.gpu, fs.n_forests(), fs.node_off.data(), fs.label.data(), fs.ref.data(),
+    hip_check(carmel_hip_forests_create(&F, o.gpu, fs.n_forests(), fs.node_off.data(), fs.label.data(), fs.ref.data(),
                                     fs.next.data(), n_rules, logw.data(), group_off.size() - 1, group_off.data(),
                                     group_rule.data()),
           "carmel_hip_forests_create");
@@ -349,14 +309,14 @@ int main(int argc, char** argv) {
     auto viterbi_text = [&](const std::vector<double>& sum, uint64_t every) {
       const uint64_t nf = fs.n_forests();
       std::vector<double> best(nf);
-      check(carmel_hip_forests_viterbi(F, best.data()), "carmel_hip_forests_viterbi");
+      hip_check(carmel_hip_forests_viterbi(F, best.data()), "carmel_hip_forests_viterbi");
       const uint32_t cap = std::max<uint32_t>(1, carmel_hip_forests_max_sample(F));
       std::vector<uint32_t> rules(cap), arity(cap);
       std::string out;
       for (uint64_t f = 0; f < nf; ++f) {
         if ((f + 1) % every) continue;
         uint32_t n = 0;
-        check(carmel_hip_forests_get_viterbi(F, f, rules.data(), arity.data(), &n), "carmel_hip_forests_get_viterbi");
+        hip_check(carmel_hip_forests_get_viterbi(F, f, rules.data(), arity.data(), &n), "carmel_hip_forests_get_viterbi");
         char pct[64];
         std::snprintf(pct, sizeof pct, "%g", 100 * std::exp(best[f] - sum[f]));
         out += format_weight(best[f], style) + "/" + format_weight(sum[f], style) + "=" + pct + "% ";
@@ -410,18 +370,18 @@ int main(int argc, char** argv) {
           } else
             ++p;
         }
-        check(carmel_hip_forests_set_alphas(F, al.data(), (uint32_t)al.size()), "carmel_hip_forests_set_alphas");
+        hip_check(carmel_hip_forests_set_alphas(F, al.data(), (uint32_t)al.size()), "carmel_hip_forests_set_alphas");
       }
       const size_t per_run = (size_t)o.crp + 1;
       std::vector<double> lp(per_run * ((size_t)go.restarts + 1));
-      check(carmel_hip_forests_set_prior_inference(F, o.pi_stddev, o.pi_global, o.pi_local, (uint32_t)std::max(0L, o.pi_start),
+      hip_check(carmel_hip_forests_set_prior_inference(F, o.pi_stddev, o.pi_global, o.pi_local, (uint32_t)std::max(0L, o.pi_start),
                                                    (uint32_t)std::max(0L, o.pi_end)),
             "carmel_hip_forests_set_prior_inference");
-      check(carmel_hip_forests_gibbs(F, &go, o.alpha, lp.data(), nullptr), "carmel_hip_forests_gibbs");
+      hip_check(carmel_hip_forests_gibbs(F, &go, o.alpha, lp.data(), nullptr), "carmel_hip_forests_gibbs");
       std::vector<double> ptrace(lp.size() * 6, 0.0), pcum(group_off.size() + 1, 1.0);
       uint32_t n_scales = 0;
-      check(carmel_hip_forests_prior_trace(F, ptrace.data(), (uint32_t)per_run, pcum.data(), (uint32_t)pcum.size(), &n_scales),
-            "carmel_hip_forests_prior_trace");
+      hip_check(carmel_hip_forests_prior_trace(F, ptrace.data(), (uint32_t)per_run, pcum.data(), (uint32_t)pcum.size(), &n_scales),
+                "carmel_hip_forests_prior_trace");
       for (size_t i = 0; i < lp.size(); ++i) {
         if (go.restarts && i % per_run == 0)  // gibbs.hpp:897
           log << "(random restart " << i / per_run << " of " << go.restarts << "): \n";
@@ -440,8 +400,8 @@ int main(int argc, char** argv) {
       if (o.print_counts_to > o.print_counts_from || o.print_norms_to > o.print_norms_from) {
         std::ostringstream tab;
         std::vector<double> fx(n_rules), fw(n_rules);
-        check(carmel_hip_forests_final_counts(F, fx.data()), "carmel_hip_forests_final_counts");
-        check(carmel_hip_forests_get_weights(F, fw.data()), "carmel_hip_forests_get_weights");
+        hip_check(carmel_hip_forests_final_counts(F, fx.data()), "carmel_hip_forests_final_counts");
+        hip_check(carmel_hip_forests_get_weights(F, fw.data()), "carmel_hip_forests_get_weights");
         std::vector<int64_t> norm_of(n_rules, -1);
         uint32_t nnorm = 0;
         for (size_t g = 0; g + 1 < group_off.size(); ++g)
@@ -495,7 +455,7 @@ int main(int argc, char** argv) {
         std::vector<uint32_t> buf(std::max<uint32_t>(1, carmel_hip_forests_max_sample(F)));
         for (uint64_t f = 0; f < fs.n_forests(); ++f) {
           uint32_t n = 0;
-          check(carmel_hip_forests_get_sample(F, f, buf.data(), &n), "carmel_hip_forests_get_sample");
+          hip_check(carmel_hip_forests_get_sample(F, f, buf.data(), &n), "carmel_hip_forests_get_sample");
           for (uint32_t k = 0; k < n; ++k) of << (k ? " " : "") << buf[k];
           of << "\n";
         }
@@ -540,7 +500,7 @@ int main(int argc, char** argv) {
       auto watch_report = [&]() {
         if (watch_members.empty()) return;
         std::vector<double> cw(n_rules);
-        check(carmel_hip_forests_get_weights(F, cw.data()), "carmel_hip_forests_get_weights");
+        hip_check(carmel_hip_forests_get_weights(F, cw.data()), "carmel_hip_forests_get_weights");
         auto gt = [&](uint32_t a, uint32_t b) { return cw[a] > cw[b]; };  // indirect_gt over the rule weights
         const size_t size = watch_members.size();
         const size_t depth = std::min<size_t>((size_t)std::max<long>(o.watch_depth, 0), size);
@@ -577,7 +537,7 @@ int main(int argc, char** argv) {
         const bool watch_it = m_steps <= o.watch_period || (o.watch_period && m_steps % o.watch_period == 0);
         const bool ck_vit = watch_it && o.viterbi_per > 0, ck_pfc = watch_it && o.per_forest_counts_per > 0;
         std::vector<double> fsum(ck_vit ? fs.n_forests() : 0);
-        check(carmel_hip_forests_estimate(F, o.prior_counts, &alp, &n_zero, ck_vit ? fsum.data() : nullptr), "carmel_hip_forests_estimate");
+        hip_check(carmel_hip_forests_estimate(F, o.prior_counts, &alp, &n_zero, ck_vit ? fsum.data() : nullptr), "carmel_hip_forests_estimate");
         if (ck_vit || ck_pfc) {
           const std::string suffix = ".restart." + std::to_string(restart + 1) + ".iteration." + std::to_string(m_steps + 1);
           if (ck_vit) spit(o.checkpoint_prefix + ".viterbi" + suffix, viterbi_text(fsum, (uint64_t)o.viterbi_per));
@@ -593,7 +553,7 @@ int main(int argc, char** argv) {
         log << ")";
         if (alp > best || very_first) {
           best = alp;
-          check(carmel_hip_forests_get_weights(F, best_w.data()), "carmel_hip_forests_get_weights");
+          hip_check(carmel_hip_forests_get_weights(F, best_w.data()), "carmel_hip_forests_get_weights");
           log << " (new best)";
         }
         very_first = false;
@@ -612,17 +572,17 @@ int main(int argc, char** argv) {
           break;
         }
         double delta = 0;
-        check(carmel_hip_forests_maximize(F, o.prior_counts, o.add_k, o.zero_zerocounts ? 1 : 0, &delta),
-              "carmel_hip_forests_maximize");
+        hip_check(carmel_hip_forests_maximize(F, o.prior_counts, o.add_k, o.zero_zerocounts ? 1 : 0, &delta),
+                  "carmel_hip_forests_maximize");
         // FForests::maximize's tail (forest-em.hpp:638-653): on a watch iteration the parameters and the counts they were
         // normalised from are dumped (dump_params :172-189) and the counts above the thresholds counted
         if (m_steps <= o.watch_period || (o.watch_period && m_steps % o.watch_period == 0)) {
           watch_report();
           if (o.checkpoint_parameters || count_report) {
             std::vector<double> cw(n_rules), cc(n_rules);
-            check(carmel_hip_forests_get_counts(F, o.prior_counts, cc.data()), "carmel_hip_forests_get_counts");
+            hip_check(carmel_hip_forests_get_counts(F, o.prior_counts, cc.data()), "carmel_hip_forests_get_counts");
             if (o.checkpoint_parameters) {
-              check(carmel_hip_forests_get_weights(F, cw.data()), "carmel_hip_forests_get_weights");
+              hip_check(carmel_hip_forests_get_weights(F, cw.data()), "carmel_hip_forests_get_weights");
               const std::string suffix = ".restart." + std::to_string(restart + 1) + ".iteration." + std::to_string(m_steps + 1);
               const std::string wf = o.checkpoint_prefix + ".params" + suffix, cf = o.checkpoint_prefix + ".counts" + suffix;
               std::vector<double> lc(n_rules);
@@ -656,24 +616,24 @@ int main(int argc, char** argv) {
       --restarts_left;
       log << "\nRandom restart - " << restarts_left << " remaining.\n";
       std::vector<double> rw(n_rules);
-      check(carmel_hip_forests_get_weights(F, rw.data()), "carmel_hip_forests_get_weights");
+      hip_check(carmel_hip_forests_get_weights(F, rw.data()), "carmel_hip_forests_get_weights");
       randomize(rw, restart + 1);
-      check(carmel_hip_forests_set_weights(F, rw.data()), "carmel_hip_forests_set_weights");
+      hip_check(carmel_hip_forests_set_weights(F, rw.data()), "carmel_hip_forests_set_weights");
       }
       // FForests::save_best / restore_best act only when random restarts were asked for (save_best_enable = restarts,
       // forest-em.hpp:363, 660-671): otherwise the parameters stay as the last M-step left them
-      if (o.restarts > 0) check(carmel_hip_forests_set_weights(F, best_w.data()), "carmel_hip_forests_set_weights");
+      if (o.restarts > 0) hip_check(carmel_hip_forests_set_weights(F, best_w.data()), "carmel_hip_forests_set_weights");
       log << "Best average log-prob=" << best << "\n";
     }
-    check(carmel_hip_forests_get_weights(F, logw.data()), "carmel_hip_forests_get_weights");
+    hip_check(carmel_hip_forests_get_weights(F, logw.data()), "carmel_hip_forests_get_weights");
     if (o.outcounts_file != "-0") {
       std::vector<double> counts(n_rules);
       // FForests::write_counts prints the count table as the LAST estimate of the EM loop left it (forest-em-params.cpp:121-122)
       // -- the counts under the parameters of that estimate, one M-step behind the final ones when the loop ended after a
       // maximize; only a run without any estimate (the sampler, -i 0) collects them now
       if (o.crp > 0 || o.max_iter <= 0)
-        check(carmel_hip_forests_estimate(F, o.prior_counts, nullptr, nullptr, nullptr), "carmel_hip_forests_estimate");
-      check(carmel_hip_forests_get_counts(F, o.prior_counts, counts.data()), "carmel_hip_forests_get_counts");
+        hip_check(carmel_hip_forests_estimate(F, o.prior_counts, nullptr, nullptr, nullptr), "carmel_hip_forests_estimate");
+      hip_check(carmel_hip_forests_get_counts(F, o.prior_counts, counts.data()), "carmel_hip_forests_get_counts");
       std::vector<double> lc(n_rules);
       for (uint32_t r = 0; r < n_rules; ++r) lc[r] = counts[r] > 0 ? std::log(counts[r]) : -std::numeric_limits<double>::infinity();
       log << "Writing trained counts to " << o.outcounts_file << "\n";
@@ -693,7 +653,7 @@ int main(int argc, char** argv) {
       log << "Repeating final iteration ...";
       const uint64_t nf = fs.n_forests();
       std::vector<double> sum(nf);
-      check(carmel_hip_forests_estimate(F, o.prior_counts, nullptr, nullptr, sum.data()), "carmel_hip_forests_estimate");
+      hip_check(carmel_hip_forests_estimate(F, o.prior_counts, nullptr, nullptr, sum.data()), "carmel_hip_forests_estimate");
       if (o.outviterbi_file != "-0") spit(o.outviterbi_file, viterbi_text(sum, 1));
       if (o.out_pfc_file != "-0") {
         // FForests::operator()(rule, inside, norm_outside) (forest-em.hpp:383-389) adds a forest's counts to the global table
@@ -715,7 +675,7 @@ int main(int argc, char** argv) {
       std::vector<double> lc;
       if (o.crp <= 0 && o.max_iter > 0) {
         std::vector<double> counts(n_rules);
-        check(carmel_hip_forests_get_counts(F, o.prior_counts, counts.data()), "carmel_hip_forests_get_counts");
+        hip_check(carmel_hip_forests_get_counts(F, o.prior_counts, counts.data()), "carmel_hip_forests_get_counts");
         lc.resize(n_rules);
         for (uint32_t r = 0; r < n_rules; ++r) lc[r] = counts[r] > 0 ? std::log(counts[r]) : -std::numeric_limits<double>::infinity();
       }

@@ -322,7 +322,7 @@ def train(fb, opts=None, log=None):
             break
         lp, wlp = fb.estimate()
         # a corpus probability within two ulps per pair of 1 counts as 1: the reference's log-domain arithmetic lands on ln P = 0
-        # exactly there and its convergence test divides zero by zero (host/carmel_main.cpp snap_certain)
+        # exactly there and its convergence test divides zero by zero (host/carmel_em.cpp snap_certain)
         tol = 4.45e-16 * max(st["n_pairs"], 1)
         lp, wlp = (0.0 if abs(lp) <= tol else lp), (0.0 if abs(wlp) <= tol else wlp)
         new_ppx = -wlp / W  # ln of p.ppxper(totalEmpiricalWeight)  (weight.h:311)

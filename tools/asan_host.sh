@@ -6,7 +6,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${TMPDIR:-/tmp}/carmel_asan
 mkdir -p $OUT
 g++ -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer -shared -I$ROOT/include \
-    $ROOT/carmel_amd/csrc/lattice.cpp $ROOT/carmel_amd/csrc/host_api.cpp $ROOT/carmel_amd/csrc/unrolled.cpp \
+    $ROOT/carmel_amd/csrc/lattice.cpp $ROOT/carmel_amd/csrc/host_api.cpp $ROOT/carmel_amd/csrc/unrolled.cpp $ROOT/carmel_amd/csrc/options.cpp \
     -o $OUT/libcarmel_host_asan.so -lpthread
 cat > $OUT/run.py <<PY
 import ctypes as C, numpy as np, sys
@@ -38,7 +38,7 @@ LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so
 # the front end's host-only paths (reader, writer, composition with and without -a, --normby / --number-from /
 # --write-loaded) under the same sanitizers, linked against the (uninstrumented) library; nothing here touches a GPU
 B=$OUT/carmel_asan_bin
-g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I$ROOT/include $ROOT/carmel_amd/csrc/host/carmel_main.cpp \
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I$ROOT/include $ROOT/carmel_amd/csrc/host/carmel_*.cpp \
     -o $B -L$ROOT/carmel_amd -lcarmel_hip -Wl,-rpath,$ROOT/carmel_amd -lpthread
 G=$ROOT/tests/golden
 export ASAN_OPTIONS=detect_leaks=0 CARMEL_TRAINED_DIR=$OUT
