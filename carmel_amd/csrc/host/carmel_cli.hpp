@@ -97,6 +97,7 @@ struct Options {
   long kpaths = 0;  // -k n (carmel.cc:1021): best paths per line; only n = 1 with -b / -i (batch decoding, decode_batch)
   long kbest = 0;   // --kbest=N: N best paths per line (print_kbest(N, ...), carmel.cc:379-397), where -k 1 is accepted
   bool have_kbest = false;
+  bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };
 

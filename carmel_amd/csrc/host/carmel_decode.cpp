@@ -5,6 +5,8 @@
 // per-line composition, which is never built, and is refused before this is reached.
 // --kbest=N prints, for every line, its N best derivations best first and then print_kbest's fill lines up to N
 // (carmel_hip_decode_kbest, csrc/decode_kbest.hip); the summary multiplies each line's first path, as with -k 1.
+// --sum-paths (carmel's --sum) adds every line's sum of all paths (post_compose's sum_acyclic_paths, carmel.cc:555-599; carmel_hip_decode_sum,
+// csrc/decode_sum.hip) to the report on stderr; what goes to stdout does not change.
 #include <cctype>
 #include "carmel_cli.hpp"
 using namespace carmel_host;
@@ -27,11 +29,15 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   std::vector<const HArc*> arc_of;
   size_t n_0prob = 0;
   double n_prob = 0, prod_viterbi = 0;
+  // --sum-paths (post_compose, carmel.cc:555-599): the lines whose sum of all paths is not zero, and the product of those sums
+  double pre_n_prob = 0, prod_sum = 0;
 
   int read_lines(const std::string& text, bool side_out);
   void decode(carmel_hip_decoder* d, size_t kbest);
+  void sum_paths(carmel_hip_decoder* d);
   void format_path(uint64_t p, std::string& buf) const;
   void print_paths(size_t kbest, bool quiet);
+  void log_ppx(double n_pairs, double prod, size_t n_0) const;
   void report() const;
 };
 
@@ -95,6 +101,25 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
     std::cerr << "timing: decode " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
               << " s (kernels " << kms * 1e-3 << " s)\n";
   }
+}
+
+// every line's sum of all paths, multiplied in line order over the lines that have a derivation
+void Batch::sum_paths(carmel_hip_decoder* d) {
+  const size_t n = lines.size();
+  std::vector<double> sums(n);
+  const auto t0 = std::chrono::steady_clock::now();
+  hip_check(carmel_hip_decode_sum(d, n, off.data(), sym.data(), sums.data()), "carmel_hip_decode_sum");
+  if (timing_on()) {
+    double kms = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    std::cerr << "timing: sum " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+              << " s (kernels " << kms * 1e-3 << " s)\n";
+  }
+  for (size_t l = 0; l < n; ++l)
+    if (sums[l] > kNegInf) {
+      ++pre_n_prob;
+      prod_sum += sums[l];
+    }
 }
 
 // one path of a line into buf, as path_print writes it
@@ -164,18 +189,32 @@ void Batch::print_paths(size_t kbest, bool quiet) {
   std::cout << std::flush;
 }
 
-// report_batch (carmel.cc:355-376) with log_ppx (:306-318) and Weight::print_ppx (weight.h:321-329)
+// log_ppx (carmel.cc:306-318) with Weight::print_ppx (weight.h:321-329)
+void Batch::log_ppx(double n_pairs, double prod, size_t n_0) const {
+  std::cerr << "product of probs=" << format_weight(prod, ws) << ", probability=" << base2(prod);
+  if (n_symbols) std::cerr << " per-input-symbol-perplexity(N=" << n_symbols << ")=" << base2(ppxper(prod, n_symbols));
+  if (n_pairs) std::cerr << " per-line-perplexity(N=" << n_pairs << ")=" << base2(ppxper(prod, n_pairs));
+  if (n_0) std::cerr << ", excluding " << n_0 << " 0 probabilities (i.e. real ppx is infinite).";
+  std::cerr << std::endl;
+}
+
+// report_batch (carmel.cc:354-377)
 void Batch::report() const {
   const size_t n = lines.size();
+  if (o.sum && pre_n_prob) {  // the lines post_compose saw: those with a derivation (the name passed is " inputs", carmel.cc:361)
+    std::cerr << "Derivations found for all " << pre_n_prob << "  inputs.\n";
+    log_ppx(pre_n_prob, prod_sum, 0);
+  }
   if (n_0prob)
     std::cerr << "No derivations found for " << n_0prob << " of " << n << " inputs.\n";
   else
     std::cerr << "Derivations found for all " << n << " inputs.\n";
-  std::cerr << "Viterbi (best path) product of probs=" << format_weight(prod_viterbi, ws) << ", probability=" << base2(prod_viterbi);
-  if (n_symbols) std::cerr << " per-input-symbol-perplexity(N=" << n_symbols << ")=" << base2(ppxper(prod_viterbi, n_symbols));
-  if (n_prob) std::cerr << " per-line-perplexity(N=" << n_prob << ")=" << base2(ppxper(prod_viterbi, n_prob));
-  if (n_0prob) std::cerr << ", excluding " << n_0prob << " 0 probabilities (i.e. real ppx is infinite).";
-  std::cerr << std::endl;
+  std::cerr << "Viterbi (best path) ";
+  log_ppx(n_prob, prod_viterbi, n_0prob);
+  if (o.sum) {
+    std::cerr << "Sum (all paths) ";
+    log_ppx(n_prob, prod_sum, n_0prob);
+  }
 }
 }  // namespace
 
@@ -200,6 +239,7 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
   } guard{d};
   const size_t kbest = o.have_kbest ? (size_t)o.kbest : 1;  // output lines per input line
   b.decode(d, kbest);
+  if (o.sum) b.sum_paths(d);
   b.print_paths(kbest, quiet);
   b.report();
   return 0;

@@ -28,6 +28,7 @@ static int print_help() {
                "--print-counts-to= --print-norms-from= --print-norms-to= --width= ... ; several GPUs: --gpus=N --exchange=; "
                "batch 1-best decoding: -b -i -s -r -k 1 with -I / -O / -@ (-Q -W -E); "
                "k-best decoding: --kbest=N (N <= 1024) in place of -k 1; "
+               "all-paths sums in the decoding report: --sum-paths with -b / -i (carmel's --sum; no epsilon cycles); "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -51,6 +52,8 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
       throw UsageError("-k without -I, -O or -@ (the arc path form: state names of a per-line composition) is not implemented");
   } else if (o.flags[(unsigned)'s'] || o.flags[(unsigned)'r'])
     throw UsageError("-s / -r apply to batch decoding (-b or -i with -k 1)");
+  else if (o.sum)
+    throw UsageError("--sum-paths applies to batch decoding (-b or -i with -k 1 or --kbest=N)");
   return decoding;
 }
 

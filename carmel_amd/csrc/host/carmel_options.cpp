@@ -114,6 +114,10 @@ Options parse_args(int argc, char** argv) {
         o.kbest = std::atol(v.c_str());
         o.have_kbest = true;
       }
+      else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
+        o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
+      else if (k == "sum")
+        throw UsageError("option --sum is not implemented under that name; with -b or -i use --sum-paths");
       else if (k == "disk-cache-derivations") {
         // carmel.cc:243-246, fst.h:1057-1076: the reference spills its derivation cache to disk when it outgrows memory (and
         // without -? rebuilds every pair's derivations in every iteration, cached_derivs.h:60-101).  Here: when the lattices of

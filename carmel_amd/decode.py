@@ -4,6 +4,7 @@ csrc/decode_kbest.hip).
     d = Decoder(wfst, side=0)          # side 0: lines are input strings; 1: output strings (carmel -r)
     best, paths = d.decode(lines)      # lines: sequences of symbol ids of that side's alphabet
     weights, kpaths = d.decode_kbest(lines, k)
+    sums = d.sum(lines)                # ln of every line's sum over ALL its derivations (carmel -b --sum; csrc/decode_sum.hip)
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -67,6 +68,15 @@ class Decoder(object):
             weights.append(logw[a:b].copy())
             paths.append([arcs[int(path_off[p]):int(path_off[p + 1])].copy() for p in range(a, b)])
         return weights, paths
+
+    def sum(self, lines):
+        """-> f64 array: per line, the ln of the sum over all its derivations of their weights (-inf: no derivation)"""
+        lines = [np.asarray(x, dtype=np.uint32) for x in lines]
+        off = u64(np.concatenate([[0], np.cumsum([len(x) for x in lines], dtype=np.uint64)]))
+        sym = u32(np.concatenate(lines)) if off[-1] else np.zeros(1, np.uint32)
+        out = np.empty(len(lines))
+        check(lib.carmel_hip_decode_sum(self._h, len(lines), ptr(off), ptr(sym), ptr(out)), "carmel_hip_decode_sum")
+        return out
 
     def last_ms(self):
         ms = C.c_double()

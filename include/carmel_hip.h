@@ -569,6 +569,17 @@ int carmel_hip_decoder_kbest_size(carmel_hip_decoder* d, uint64_t* n_paths, uint
  * arcs[path_off[p] .. path_off[p + 1]) in path order; path_off has n_paths + 1 entries */
 int carmel_hip_decoder_get_kbest(carmel_hip_decoder* d, double* path_logw, uint64_t* path_off, uint32_t* arcs);
 
+/* ---- batch all-paths sums (carmel -b --sum; csrc/decode_sum.hip) ----
+ * Replaces: post_compose's sum_acyclic_paths per line (carmel.cc:555-599, fst.h:1183-1191, graph.h:391-419).  Lines as for
+ * carmel_hip_decode.  sum_logw[l] = ln of the sum, over ALL derivations of line l (as carmel_hip_decode_kbest defines them), of
+ * the product of their arcs' weights; -inf = no derivation.  It is the forward pass of the 1-best trellis in the log semiring,
+ * f64, every node's terms added in one fixed order: the result does not depend on chunking, memory tier or launch
+ * order, and a line with a single derivation gets its arcs' logs added in path order.  If the matched side's epsilon arcs have a
+ * cycle the call fails with CARMEL_HIP_ERR_UNSUPPORTED, naming the epsilon cycle, and nothing is written (the reference's sum is
+ * "acyclic-correct only", carmel.cc:1787).  May alternate with carmel_hip_decode and carmel_hip_decode_kbest on one handle, and
+ * sees the weights of carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers this kernel too. */
+int carmel_hip_decode_sum(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, double* sum_logw);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;

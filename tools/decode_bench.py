@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Batch 1-best and k-best decoding on the MI355X (csrc/decode.hip, csrc/decode_kbest.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
+"""Batch 1-best and k-best decoding and all-paths sums on the MI355X (csrc/decode.hip, csrc/decode_kbest.hip,
+csrc/decode_sum.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
 the output side as in `carmel -qbsriWIEk 1`) over tagging.data.noe repeated to about --lines lines, then the front end's
 end-to-end time for the tutorial's three decode commands.  Every --kbest K adds the same lines through carmel_hip_decode_kbest
 with that K ("kbest": kernel and call time, paths returned, and for K = 1 the ratio to the 1-best kernels' time of this run).
+--sum adds the same lines through carmel_hip_decode_sum, timed in the same run ("sum": kernel and call time, lines per second,
+the ratio to the 1-best kernels' time), and writes that run's figures to --sum-out (profiles/decode_sum_bench.json).
 Prints one JSON object.
 
-    python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...]
+    python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...] [--sum]
 
 The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
 on the weights); the cluster and cipher commands use their committed trained members."""
@@ -40,6 +43,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fst", default=os.path.join(G, "tagging.fst"))
     ap.add_argument("--kbest", type=int, action="append", default=[], metavar="K")
+    ap.add_argument("--sum", action="store_true")
+    ap.add_argument("--sum-out", default=os.path.join(ROOT, "profiles", "decode_sum_bench.json"))
     a = ap.parse_args()
     from carmel_amd.decode import Decoder
     from carmel_amd.model import Wfst
@@ -73,6 +78,20 @@ def main():
                          "paths": int(len(logw)), "path_arcs": int(len(arcs)),
                          "rank0_equals_1best": bool(np.array_equal(logw[line_paths[:-1][np.diff(line_paths) > 0].astype(np.int64)],
                                                                    best[~np.isneginf(best)]))}
+    sums = None
+    if a.sum:
+        d.sum(lines[:1000])
+        kms_s, wall_s = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            total = d.sum(lines)
+            wall_s.append((time.perf_counter() - t0) * 1e3)
+            kms_s.append(d.last_ms())
+        sums = {"kernel_ms": float(np.median(kms_s)), "kernel_ms_all": kms_s, "call_ms": float(np.median(wall_s)),
+                "lines_per_s": len(lines) / (float(np.median(kms_s)) * 1e-3), "no_derivation": int(np.isneginf(total).sum()),
+                "sum_ln": float(total[~np.isneginf(total)].sum()), "viterbi_ln": float(best[~np.isneginf(best)].sum()),
+                # (a line with one derivation sums its arcs in path order, the 1-best weight is added from the end: the last bit may differ)
+                "max_1best_minus_sum": float(np.max(best[~np.isneginf(best)] - total[~np.isneginf(best)]))}
     d.close()
     n_pos = int(sum(len(x) for x in lines))
     # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
@@ -101,6 +120,14 @@ def main():
         e2e[name] = {"rc": p.returncode, "seconds": time.perf_counter() - t0,
                      "timing": [l for l in p.stderr.split("\n") if l.startswith("timing: decode")]}
     res["end_to_end"] = e2e
+    if sums:
+        sums["kernel_ms_over_1best"] = sums["kernel_ms"] / kms
+        res["sum"] = sums
+        with open(a.sum_out, "w") as f:
+            json.dump({"workload": res["workload"], "machine": res["machine"], "reps": a.reps,
+                       "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
+                                    "lines_per_s": res["lines_per_s"]}, "sum": sums}, f)
+            f.write("\n")
     shutil.rmtree(tmp)
     print(json.dumps(res))
 
