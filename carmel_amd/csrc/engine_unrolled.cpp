@@ -12,7 +12,7 @@
 #include "unrolled_args.hpp"
 #include <numeric>
 
-// The rank-1 dense form (dense.hpp).  Eligible: a cascade, at most DENSE_MAX_STATES states, no *e*:*e* arcs, and for every
+// The rank-1 dense form (dense.hpp).  Eligible: a cascade, at most DENSE_MAX_STATES states, at most 16 *e*:*e* arcs, all count-free, and for every
 // arc (s -> s', symbol c) the parameters of its chain that collect NO counts are the same for all c (they make A[s][s']),
 // the ones that do are the same for all s (at most one: B[c][s'] and its accumulator), and an arc exists exactly when both
 // its A and its B entry do.  Returns false (with t->dense clear) when the model is not of that shape.
@@ -163,6 +163,18 @@ int unrolled_try_build(carmel_hip_trainer* t, int host_threads, uint8_t* has_der
   if (!build_unrolled(t->w, t->corpus, host_threads, M)) return CARMEL_HIP_OK;
   // accumulator slots: the arc itself, or the unlocked parameters of its chain
   const uint64_t n_arcs = t->w.n_arcs;
+  {
+    // Both unrolled sweeps work in the scaled LINEAR domain, a position at a time.  An arc whose weight underflows a double
+    // is an absent arc to the table-walking sweep (exp(ln w) = 0), and where A[s][s'] * B[c][s'] underflows for every s' of
+    // a position the dense sweep divides by a zero scale: NaN in ln p and in every count.  Explicit lattices hold
+    // logarithms and sweep such a model correctly, so a model with a (composed) arc below e^-700 keeps them.  The test is
+    // made on the weights as they stand when the lattices are built.
+    std::vector<double> lw(n_arcs);
+    HIPCHK(hipMemcpyAsync(lw.data(), t->arc_logw.p, n_arcs * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    for (uint64_t a = 0; a < n_arcs; ++a)
+      if (lw[a] < -700.0 && lw[a] > -std::numeric_limits<double>::infinity()) return CARMEL_HIP_OK;
+  }
   std::vector<uint16_t> arc_slot((size_t)n_arcs * UNROLLED_MAX_CHAIN, (uint16_t)UNROLLED_NO_SLOT);
   uint32_t n_slots = 0;
   std::vector<double> uses, wprior;
