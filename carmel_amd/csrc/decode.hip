@@ -30,33 +30,21 @@
 //
 // d_i and d_{i+1} are two rows of |Q| doubles: in LDS when 16 |Q| bytes fit 64 KiB (|Q| <= 4096), otherwise in a global scratch
 // buffer per line (the "global tier": correct, not fast).  The back-pointers are walked afterwards by one lane per line
-// (decode_walk_kernel), once to count a path's arcs and once to write them in path order.
-// The tables, the handle and the constants are in decode.hpp, shared with the k-best decoder (decode_kbest.hip).
+// (decode_paths.hip's decode_walk_kernel), once to count a path's arcs and once to write them in path order.
+// The tables, the handle, the constants and the host drivers are in decode.hpp, shared with the k-best decoder
+// (decode_kbest.hip) and the all-paths sum (decode_sum.hip); this kernel alone closes a cyclic epsilon subgraph.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <memory>
-#include <numeric>
 #include <string>
 #include <vector>
 #include "decode.hpp"
 #include "engine.hpp"
 
 namespace {
-struct DecodeLines {
-  const uint64_t* off;     // chunk-local CSR of the lines' symbols
-  const uint32_t* sym;
-  const uint32_t* order;   // launch order: chunk-local line index of block b
-  const uint64_t* bp_off;  // [n + 1]: each line's (len + 1) x |Q| back-pointers
-  uint32_t* bp;
-  double* rows;            // global tier: 2 |Q| doubles per line (nullptr in the LDS tier)
-  double* best;            // [n]
-  int* err;
-};
-
 // close `row` (position i's values) over the epsilon arcs; `bpr` is that position's back-pointer row
 __device__ void eps_close(const DecodeTables& T, double* row, uint32_t* bpr, int lane, int* err) {
   if (!T.eps_cyclic) {
@@ -103,7 +91,7 @@ __device__ void eps_close(const DecodeTables& T, double* row, uint32_t* bpr, int
 }
 
 template <bool kLds>
-__global__ void __launch_bounds__(kLanes) decode_trellis_kernel(DecodeTables T, DecodeLines D) {
+__global__ void __launch_bounds__(kLanes) decode_trellis_kernel(DecodeTables T, DecodeLines D, DecodePaths P) {
   extern __shared__ double lds_rows[];
   const int lane = threadIdx.x;
   const uint32_t line = D.order[blockIdx.x];
@@ -112,14 +100,14 @@ __global__ void __launch_bounds__(kLanes) decode_trellis_kernel(DecodeTables T, 
   double* nxt = cur + Q;
   const uint64_t s0 = D.off[line];
   const uint32_t n = (uint32_t)(D.off[line + 1] - s0);
-  uint32_t* bp = D.bp + D.bp_off[line];
+  uint32_t* bp = P.bp_arc + P.bp_off[line];
   const double ninf = -std::numeric_limits<double>::infinity();
   for (uint32_t q = lane; q < Q; q += kLanes) {
     cur[q] = q == 0 ? 0.0 : ninf;
     bp[q] = kNone;
   }
   __syncthreads();
-  eps_close(T, cur, bp, lane, D.err);
+  eps_close(T, cur, bp, lane, P.err);
   for (uint32_t i = 0; i < n; ++i) {
     uint32_t* bpn = bp + (size_t)(i + 1) * Q;
     for (uint32_t q = lane; q < Q; q += kLanes) {
@@ -146,54 +134,22 @@ __global__ void __launch_bounds__(kLanes) decode_trellis_kernel(DecodeTables T, 
         }
       }
     __syncthreads();
-    eps_close(T, nxt, bpn, lane, D.err);
+    eps_close(T, nxt, bpn, lane, P.err);
     double* t = cur;
     cur = nxt;
     nxt = t;
   }
-  if (lane == 0) D.best[line] = cur[T.final_state];
-}
-
-// one lane per line walks the back-pointers from (n, final) to (0, start): kWrite = false counts the path's arcs into len[line]
-// and replaces best[line] by the arcs' weights added from the end (the reference's k-best cost); kWrite = true writes the arcs
-// in path order at path[path_off[line] ..)
-template <bool kWrite>
-__global__ void decode_walk_kernel(uint32_t n_lines, uint32_t n_states, uint32_t final_state, uint64_t n_arcs, const uint64_t* off,
-                                   const uint64_t* bp_off, const uint32_t* bp, double* best, const uint32_t* a_src,
-                                   const uint8_t* a_eps, const double* a_w, uint32_t* len, const uint64_t* path_off, uint32_t* path,
-                                   int* err) {
-  const uint32_t line = blockIdx.x * blockDim.x + threadIdx.x;
-  if (line >= n_lines) return;
-  if (!(best[line] > -std::numeric_limits<double>::infinity())) {
-    if (!kWrite) len[line] = 0;
-    return;
-  }
-  uint32_t i = (uint32_t)(off[line + 1] - off[line]), q = final_state;
-  const uint32_t* b = bp + bp_off[line];
-  const uint64_t cap = (uint64_t)(i + 1) * n_states;  // no path of the trellis is longer
-  const uint32_t n_path = kWrite ? len[line] : 0;
-  uint32_t steps = 0;
-  double w = 0.0;
-  while (true) {
-    const uint32_t a = b[(size_t)i * n_states + q];
-    if (a == kNone) break;
-    if (a >= n_arcs || steps >= cap || (kWrite && steps >= n_path) || (!a_eps[a] && i == 0)) {
-      atomicOr(err, kErrWalk);
-      return;
-    }
-    ++steps;
-    if (kWrite) path[path_off[line] + n_path - steps] = a;
-    w = a_w[a] + w;
-    q = a_src[a];
-    if (!a_eps[a]) --i;
-  }
-  if (i != 0 || q != 0) atomicOr(err, kErrWalk);
-  if (!kWrite) {
-    len[line] = steps;
-    best[line] = w;
-  }
+  if (lane == 0) P.n_paths[line] = cur[T.final_state] > ninf;
 }
 }  // namespace
+
+void carmel_hip::launch_decode_trellis(const carmel_hip_decoder* d, bool lds, uint32_t n, const DecodeLines& L, const DecodePaths& P,
+                                       hipStream_t s) {
+  if (lds)
+    decode_trellis_kernel<true><<<n, kLanes, 16 * (size_t)d->n_states, s>>>(d->T, L, P);
+  else
+    decode_trellis_kernel<false><<<n, kLanes, 0, s>>>(d->T, L, P);
+}
 
 int carmel_hip_decoder::upload_tables() {
   const double ninf = -std::numeric_limits<double>::infinity();
@@ -348,94 +304,19 @@ int carmel_hip_decode(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* o
                       uint64_t* path_off) {
   if (!d || !off || !best_logw || !path_off || (off[n_lines] && !sym))
     return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decode: bad argument");
-  for (uint64_t l = 0; l < n_lines; ++l)
-    if (off[l + 1] < off[l] || off[l + 1] - off[l] >= kNone) return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decode: bad line offsets");
-  HIPCHK(hipSetDevice(d->device));
-  hipStream_t s = d->stream;
-  const uint32_t Q = d->n_states;
-  const bool lds = Q <= kLdsStates && !lib_opt_off("decode_lds");
-  // lines go in chunks, in line order, whose back-pointers (and global-tier rows) fit the budget ("decode_chunk_bytes", default
-  // 1 GiB; a single line larger than it goes alone)
-  uint64_t budget = 1ull << 30;
-  if (const char* v = lib_opt("decode_chunk_bytes")) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
-  auto line_bytes = [&](uint64_t l) { return (off[l + 1] - off[l] + 1) * Q * 4ull + (lds ? 0 : 16ull * Q); };
+  if (const int rc = decode_check_lines("carmel_hip_decode", n_lines, off)) return rc;
   d->paths.clear();
+  std::vector<uint64_t> line_paths(n_lines + 1), p_off;
+  std::vector<double> p_logw;
+  const int rc = decode_paths(d, "carmel_hip_decode", 1, false, launch_decode_trellis, n_lines, off, sym, line_paths.data(), p_logw,
+                              p_off, d->paths);
+  if (rc) return rc;
   path_off[0] = 0;
-  float total_ms = 0;
-  DevBuf<uint64_t> d_off, d_bpoff, d_poff;
-  DevBuf<uint32_t> d_sym, d_order, d_bp, d_len, d_path;
-  DevBuf<double> d_rows, d_best;
-  DevBuf<int> d_err;
-  HIPCHK(d_err.alloc(1));
-  for (uint64_t lo = 0; lo < n_lines;) {
-    uint64_t hi = lo + 1, bytes = line_bytes(lo);
-    while (hi < n_lines && hi - lo < (1u << 24) && bytes + line_bytes(hi) <= budget) bytes += line_bytes(hi++);
-    const uint32_t n = (uint32_t)(hi - lo);
-    std::vector<uint64_t> h_off(n + 1), h_bpoff(n + 1);
-    for (uint32_t l = 0; l <= n; ++l) h_off[l] = off[lo + l] - off[lo];
-    h_bpoff[0] = 0;
-    for (uint32_t l = 0; l < n; ++l) h_bpoff[l + 1] = h_bpoff[l] + (h_off[l + 1] - h_off[l] + 1) * Q;
-    std::vector<uint32_t> order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t a, uint32_t b) { return h_off[a + 1] - h_off[a] > h_off[b + 1] - h_off[b]; });
-    HIPCHK(d_off.upload(h_off, s));
-    HIPCHK(d_bpoff.upload(h_bpoff, s));
-    const std::vector<uint32_t> h_sym(sym + off[lo], sym + off[hi]);  // (named: the copy is asynchronous)
-    HIPCHK(d_sym.upload(h_sym, s));
-    HIPCHK(d_order.upload(order, s));
-    HIPCHK(d_bp.alloc(h_bpoff[n]));
-    if (!lds) HIPCHK(d_rows.alloc((size_t)n * 2 * Q));
-    HIPCHK(d_best.alloc(n));
-    HIPCHK(d_len.alloc(n));
-    HIPCHK(hipMemsetAsync(d_err.p, 0, sizeof(int), s));
-    DecodeLines D{d_off.p, d_sym.p, d_order.p, d_bpoff.p, d_bp.p, lds ? nullptr : d_rows.p, d_best.p, d_err.p};
-    HIPCHK(hipEventRecord(d->ev0, s));
-    if (lds)
-      decode_trellis_kernel<true><<<n, kLanes, 16 * (size_t)Q, s>>>(d->T, D);
-    else
-      decode_trellis_kernel<false><<<n, kLanes, 0, s>>>(d->T, D);
-    HIPCHK(hipGetLastError());
-    const uint32_t wb = (n + 255) / 256;
-    decode_walk_kernel<false><<<wb, 256, 0, s>>>(n, Q, d->final_state, d->n_arcs, d_off.p, d_bpoff.p, d_bp.p, d_best.p, d->a_src.p,
-                                                 d->a_eps.p, d->a_w.p, d_len.p, nullptr, nullptr, d_err.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(d->ev1, s));
-    std::vector<uint32_t> len(n);
-    int err = 0;
-    HIPCHK(hipMemcpyAsync(best_logw + lo, d_best.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(len.data(), d_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&err, d_err.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-    total_ms += ms;
-    if (err & kErrCycle)  // kbest.h:160-166
-      return fail(CARMEL_HIP_ERR_UNSUPPORTED, "best_path_has_cycle: the best path has a cycle (an epsilon cycle of weight > 1)");
-    if (err) return fail(CARMEL_HIP_ERR_STATE, "carmel_hip_decode: inconsistent back-pointers");
-    std::vector<uint64_t> h_poff(n + 1, 0);
-    for (uint32_t l = 0; l < n; ++l) h_poff[l + 1] = h_poff[l] + len[l];
-    for (uint32_t l = 0; l < n; ++l) path_off[lo + l + 1] = path_off[lo + l] + len[l];
-    if (h_poff[n]) {
-      HIPCHK(d_poff.upload(h_poff, s));
-      HIPCHK(d_path.alloc(h_poff[n]));
-      HIPCHK(hipEventRecord(d->ev0, s));
-      decode_walk_kernel<true><<<wb, 256, 0, s>>>(n, Q, d->final_state, d->n_arcs, d_off.p, d_bpoff.p, d_bp.p, d_best.p, d->a_src.p,
-                                                  d->a_eps.p, d->a_w.p, d_len.p, d_poff.p, d_path.p, d_err.p);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(d->ev1, s));
-      const size_t at = d->paths.size();
-      d->paths.resize(at + h_poff[n]);
-      HIPCHK(hipMemcpyAsync(d->paths.data() + at, d_path.p, h_poff[n] * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(&err, d_err.p, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-      total_ms += ms;
-      if (err) return fail(CARMEL_HIP_ERR_STATE, "carmel_hip_decode: inconsistent back-pointers");
-    }
-    lo = hi;
+  for (uint64_t l = 0; l < n_lines; ++l) {  // a line has one path or none
+    const uint64_t p = line_paths[l];
+    best_logw[l] = line_paths[l + 1] > p ? p_logw[p] : -std::numeric_limits<double>::infinity();
+    path_off[l + 1] = p_off[line_paths[l + 1]];
   }
-  d->last_ms = total_ms;
   return CARMEL_HIP_OK;
 }
 

@@ -1,8 +1,12 @@
-// decode.hpp — what the 1-best decoder (decode.hip) and the k-best decoder (decode_kbest.hip) share: the prepared tables, the
-// decoder handle and the constants.  The tables are built and uploaded by carmel_hip_decoder::upload_tables (decode.hip).
+// decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip) share: the
+// prepared tables, the decoder handle, the constants, the arguments every trellis kernel takes, and the two host drivers of
+// decode_paths.hip -- the chunk driver of all three entry points and the path driver of the two that return paths.  The tables
+// are built and uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum
+// share is decode_trellis.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <functional>
 #include <vector>
 #include "engine.hpp"
 
@@ -30,6 +34,24 @@ struct DecodeTables {
   const double* e_w;
   const uint32_t* e_id;
   uint32_t n_eps;
+};
+
+// a chunk's lines, as every trellis kernel takes them: one workgroup of kLanes lanes per line
+struct DecodeLines {
+  const uint64_t* off;    // chunk-local CSR of the lines' symbols
+  const uint32_t* sym;
+  const uint32_t* order;  // launch order: chunk-local line index of block b
+  double* rows;           // global tier: a line's two rows (nullptr in the LDS tier)
+};
+
+// what a trellis kernel that records paths leaves to the walk: K slots per (position, state), slot (i |Q| + q) K + r
+struct DecodePaths {
+  const uint64_t* bp_off;  // [n + 1]: each line's (len + 1) x |Q| x K slots
+  uint32_t* bp_arc;        // the arc that enters the slot's path last (kNone: the path ends here)
+  uint16_t* bp_rank;       // the rank of that arc's source; nullptr: every rank is 0 (the 1-best trellis, 4 bytes a slot)
+  uint32_t* n_paths;       // [n]: how many of its K slots the final node of a line fills
+  int* err;
+  uint32_t K;
 };
 }  // namespace carmel_hip
 
@@ -61,3 +83,41 @@ struct carmel_hip_decoder {
   }
   int upload_tables();
 };
+
+namespace carmel_hip {
+// One chunk of a call's lines, as decode_chunks hands it to its caller.  The caller launches its kernels between begin() and end()
+// (which bracket them with the handle's events), queues its copies back and calls wait(): last_ms covers the kernels, not the copies.
+struct DecodeChunk {
+  carmel_hip_decoder* d;
+  uint64_t lo, hi;        // the chunk is lines [lo, hi) of the call
+  uint32_t n;             // hi - lo
+  const uint64_t* h_off;  // [n + 1]: L.off on the host
+  DecodeLines L;          // on the device
+  bool lds;               // the rows are in LDS
+  float ms;
+  int begin();
+  int end();   // checks the launches
+  int wait();  // the stream has drained; adds the bracket's time
+};
+
+// <who>: bad line offsets, for the entry point `who`
+int decode_check_lines(const char* who, uint64_t n_lines, const uint64_t* off);
+// The chunk driver: lines go in chunks, in line order, of fewer than `cap` lines whose cost fits the budget (option
+// "decode_chunk_bytes", default 1 GiB; a single line larger than it goes alone).  A line of len symbols costs a len + b bytes,
+// plus its two rows of row_doubles doubles in the global tier (row_doubles > kLdsStates, or option decode_lds=0).  Every chunk's
+// lines are uploaded with their launch order (longest first) and handed to `body`; d->last_ms is set if every chunk returns 0.
+int decode_chunks(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, uint64_t a, uint64_t b,
+                  uint64_t cap, uint64_t row_doubles, const std::function<int(DecodeChunk&)>& body);
+
+// launches a path-recording trellis kernel over the n lines of a chunk
+typedef void (*TrellisLaunch)(const carmel_hip_decoder* d, bool lds, uint32_t n, const DecodeLines& L, const DecodePaths& P,
+                              hipStream_t s);
+void launch_decode_trellis(const carmel_hip_decoder* d, bool lds, uint32_t n, const DecodeLines& L, const DecodePaths& P,
+                           hipStream_t s);  // the 1-best trellis (decode.hip): K = 1, no rank array
+// The path driver: per chunk the trellis `launch` with K slots a node (a rank array if `ranked`), the counting walk, the prefix
+// sums and the writing walk.  -> line_paths [n_lines + 1] (line -> paths), and per path its reported weight, the CSR of its arcs
+// and the arcs, in (line, rank) order.  Errors are reported in the name of the entry point `who`.
+int decode_paths(carmel_hip_decoder* d, const char* who, uint32_t K, bool ranked, TrellisLaunch launch, uint64_t n_lines,
+                 const uint64_t* off, const uint32_t* sym, uint64_t* line_paths, std::vector<double>& logw,
+                 std::vector<uint64_t>& path_off, std::vector<uint32_t>& arcs);
+}  // namespace carmel_hip

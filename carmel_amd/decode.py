@@ -1,5 +1,5 @@
 """Batch 1-best and k-best decoding on the GPU (carmel -b -k n; include/carmel_hip.h carmel_hip_decoder_*, csrc/decode.hip and
-csrc/decode_kbest.hip).
+csrc/decode_kbest.hip, on the drivers of csrc/decode_paths.hip).
 
     d = Decoder(wfst, side=0)          # side 0: lines are input strings; 1: output strings (carmel -r)
     best, paths = d.decode(lines)      # lines: sequences of symbol ids of that side's alphabet
@@ -17,6 +17,14 @@ import numpy as np
 from ._capi import check, f64, lib, ptr, u32, u64
 
 
+def _pack(lines):
+    """-> (off, sym): the CSR of the lines' symbols, as every decode entry point takes it"""
+    lines = [np.asarray(x, dtype=np.uint32) for x in lines]
+    off = u64(np.concatenate([[0], np.cumsum([len(x) for x in lines], dtype=np.uint64)]))
+    sym = u32(np.concatenate(lines)) if off[-1] else np.zeros(1, np.uint32)
+    return off, sym
+
+
 class Decoder(object):
     def __init__(self, wfst, side=0, device=0):
         self.n_arcs = wfst.n_arcs
@@ -32,9 +40,7 @@ class Decoder(object):
         check(lib.carmel_hip_decoder_set_weights(self._h, ptr(logw)), "carmel_hip_decoder_set_weights")
 
     def decode(self, lines):
-        lines = [np.asarray(x, dtype=np.uint32) for x in lines]
-        off = u64(np.concatenate([[0], np.cumsum([len(x) for x in lines], dtype=np.uint64)]))
-        sym = u32(np.concatenate(lines)) if off[-1] else np.zeros(1, np.uint32)
+        off, sym = _pack(lines)
         best = np.empty(len(lines))
         path_off = np.zeros(len(lines) + 1, np.uint64)
         check(lib.carmel_hip_decode(self._h, len(lines), ptr(off), ptr(sym), ptr(best), ptr(path_off)), "carmel_hip_decode")
@@ -45,9 +51,7 @@ class Decoder(object):
 
     def decode_kbest_raw(self, lines, k):
         """-> (line_paths, logw, path_off, arcs): the arrays of carmel_hip_decode_kbest / carmel_hip_decoder_get_kbest"""
-        lines = [np.asarray(x, dtype=np.uint32) for x in lines]
-        off = u64(np.concatenate([[0], np.cumsum([len(x) for x in lines], dtype=np.uint64)]))
-        sym = u32(np.concatenate(lines)) if off[-1] else np.zeros(1, np.uint32)
+        off, sym = _pack(lines)
         line_paths = np.zeros(len(lines) + 1, np.uint64)
         check(lib.carmel_hip_decode_kbest(self._h, int(k), len(lines), ptr(off), ptr(sym), ptr(line_paths)),
               "carmel_hip_decode_kbest")
@@ -71,9 +75,7 @@ class Decoder(object):
 
     def sum(self, lines):
         """-> f64 array: per line, the ln of the sum over all its derivations of their weights (-inf: no derivation)"""
-        lines = [np.asarray(x, dtype=np.uint32) for x in lines]
-        off = u64(np.concatenate([[0], np.cumsum([len(x) for x in lines], dtype=np.uint64)]))
-        sym = u32(np.concatenate(lines)) if off[-1] else np.zeros(1, np.uint32)
+        off, sym = _pack(lines)
         out = np.empty(len(lines))
         check(lib.carmel_hip_decode_sum(self._h, len(lines), ptr(off), ptr(sym), ptr(out)), "carmel_hip_decode_sum")
         return out

@@ -82,7 +82,13 @@ def test_decode_fixtures(golden_dir):
 
 
 def test_decode_kernels_use_no_scratch_memory():
-    ks = {k: v for k, v in kernels(device_asm("decode.hip")).items() if "decode_" in k}
+    """the 1-best trellis kernel in its two tiers (decode.hip), and the walk kernel that it shares with the k-best decoder in its
+    two passes (decode_paths.hip)"""
+    ks = kernels(device_asm("decode.hip"))
+    assert len(ks) == 2 and all("decode_trellis_kernel" in k for k in ks), list(ks)
+    walks = kernels(device_asm("decode_paths.hip"))
+    assert len(walks) == 2 and all("decode_walk_kernel" in k for k in walks), list(walks)
+    ks.update(walks)
     assert len(ks) == 4, list(ks)
     for name, (body, tail) in ks.items():
         m = re.search(r"; ScratchSize: (\d+)", tail)

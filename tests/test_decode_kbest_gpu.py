@@ -98,6 +98,39 @@ def test_rank_0_is_the_1best_path(seed):
         d.close()
 
 
+def test_every_line_alone_in_its_chunk_and_no_lines(hipopt):
+    """a budget below every line's cost (each line goes alone) returns the bytes of the default budget, from all three entries;
+    an empty list of lines returns empty results"""
+    from carmel_amd.decode import Decoder
+    rng = np.random.default_rng(77)
+    w = random_machine(rng, 40, 5, 160, p_eps=0.2, cyclic=False)
+    lines = lines_for(rng, w, 0, 5, 12)
+    d = Decoder(w)
+
+    def everything(ls):
+        best, paths = d.decode(ls)
+        raw = d.decode_kbest_raw(ls, 3)
+        return [best.tobytes()] + [p.tobytes() for p in paths] + [a.tobytes() for a in raw] + [d.sum(ls).tobytes()]
+
+    def nothing():
+        best, paths = d.decode([])
+        assert len(best) == 0 and paths == []
+        assert d.decode_kbest([], 3) == ([], [])
+        line_paths, logw, path_off, arcs = d.decode_kbest_raw([], 3)
+        assert list(line_paths) == [0] and len(logw) == 0 and list(path_off) == [0] and len(arcs) == 0
+        assert len(d.sum([])) == 0
+
+    try:
+        a = everything(lines)
+        assert any(len(p) for p in a[1:13])  # some line has a path
+        nothing()
+        hipopt.set("decode_chunk_bytes", "1")
+        assert everything(lines) == a
+        nothing()
+    finally:
+        d.close()
+
+
 def test_epsilon_cycle_is_refused_for_k_above_1():
     from carmel_amd._capi import CarmelHipError
     from carmel_amd.decode import Decoder

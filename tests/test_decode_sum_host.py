@@ -143,8 +143,9 @@ def test_help_names_sum():
 
 
 def test_sum_kernel_uses_no_scratch_memory():
-    ks = {k: v for k, v in kernels(device_asm("decode_sum.hip")).items() if "sum_trellis" in k}
-    assert len(ks) == 2, list(ks)  # the trellis kernel in its two tiers
+    everything = kernels(device_asm("decode_sum.hip"))
+    ks = {k: v for k, v in everything.items() if "trellis_kernel" in k and "SumNode" in k}
+    assert len(ks) == 2 and len(everything) == 2, list(everything)  # the shared trellis kernel around the sum's node, in its two tiers
     for name, (body, tail) in ks.items():
         m = re.search(r"; ScratchSize: (\d+)", tail)
         assert m and int(m.group(1)) == 0, (name, m and m.group(0))
