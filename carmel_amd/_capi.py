@@ -42,6 +42,7 @@ SYMBOLS = [
     "carmel_hip_decoder_last_ms", "carmel_hip_decoder_destroy",
     "carmel_hip_decode_kbest", "carmel_hip_decoder_kbest_size", "carmel_hip_decoder_get_kbest",
     "carmel_hip_decode_sum",
+    "carmel_hip_decode_sample",
 ]
 
 
@@ -232,6 +233,7 @@ def _load():
     lib.carmel_hip_decoder_kbest_size.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.carmel_hip_decoder_get_kbest.argtypes = [vp, vp, vp, vp]
     lib.carmel_hip_decode_sum.argtypes = [vp, C.c_uint64, vp, vp, vp]
+    lib.carmel_hip_decode_sample.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp]
     for s in SYMBOLS:  # a prototype for every entry point: without one ctypes passes Python ints as C int (64-bit seeds
         if getattr(lib, s).argtypes is None:  # and bare handles would be truncated)
             raise ImportError("carmel_amd: no ctypes prototype for %s" % s)

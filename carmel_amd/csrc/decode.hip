@@ -226,6 +226,8 @@ int carmel_hip_decoder::upload_tables() {
     h_ent_arc.push_back((uint32_t)eps.size());
     for (uint32_t L = 0; L < n_levels; ++L) h_lvl_ent[L + 1] += h_lvl_ent[L];
   }
+  std::vector<uint32_t> h_stent(Q, kNone);  // the sampler's walk finds a state's epsilon arcs through its entry
+  for (size_t e = 0; e < h_ent_dst.size(); ++e) h_stent[h_ent_dst[e]] = (uint32_t)e;
   for (uint32_t k : eps) {
     h_esrc.push_back(src[k]);
     h_edst.push_back(dst[k]);
@@ -254,9 +256,10 @@ int carmel_hip_decoder::upload_tables() {
   HIPCHK(a_w.upload(logw, s));
   HIPCHK(a_eps.upload(h_aeps, s));
   HIPCHK(eps_in.upload(h_epsin, s));
+  HIPCHK(st_ent.upload(h_stent, s));
   HIPCHK(hipStreamSynchronize(s));
   T = DecodeTables{Q, final_state, n_syms, sym_seg.p, seg_dst.p, seg_arc.p, m_src.p, m_w.p, m_id.p, n_levels, eps_cyclic ? 1 : 0,
-                   lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size()};
+                   lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size(), st_ent.p};
   return CARMEL_HIP_OK;
 }
 

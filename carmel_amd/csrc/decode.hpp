@@ -1,6 +1,7 @@
-// decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip) share: the
-// prepared tables, the decoder handle, the constants, the arguments every trellis kernel takes, and the two host drivers of
-// decode_paths.hip -- the chunk driver of all three entry points and the path driver of the two that return paths.  The tables
+// decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
+// samples decode_sample.hip) share: the prepared tables, the decoder handle, the constants, the arguments every trellis kernel
+// takes, and the host drivers of decode_paths.hip -- the chunk driver of all four entry points, the path driver of the two that
+// return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables
 // are built and uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum
 // share is decode_trellis.hpp.
 #pragma once
@@ -34,6 +35,7 @@ struct DecodeTables {
   const double* e_w;
   const uint32_t* e_id;
   uint32_t n_eps;
+  const uint32_t* st_ent;    // [n_states] -> the entry whose destination the state is (kNone: no epsilon arc enters it, or cyclic)
 };
 
 // a chunk's lines, as every trellis kernel takes them: one workgroup of kLanes lanes per line
@@ -63,13 +65,14 @@ struct carmel_hip_decoder {
   std::vector<uint32_t> src, dst, msym;  // msym: the matched-side symbol of every arc
   std::vector<double> logw;
   bool eps_cyclic = false;
-  DevBuf<uint32_t> sym_seg, seg_dst, seg_arc, m_src, m_id, lvl_ent, ent_dst, ent_arc, e_src, e_dst, e_id, a_src;
+  DevBuf<uint32_t> sym_seg, seg_dst, seg_arc, m_src, m_id, lvl_ent, ent_dst, ent_arc, e_src, e_dst, e_id, a_src, st_ent;
   DevBuf<double> m_w, e_w, a_w;
   DevBuf<uint8_t> a_eps;
   DevBuf<uint8_t> eps_in;  // [|Q|]: the state is the destination of an epsilon arc of non-zero weight (k-best: its epsilon level is >= 1)
   DecodeTables T;
   std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
-  // the last k-best decode (carmel_hip_decode_kbest): every path's reported weight, the CSR of the paths' arcs, the arcs
+  // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample): every path's reported weight, the CSR
+  // of the paths' arcs, the arcs
   std::vector<double> kb_logw;
   std::vector<uint64_t> kb_off;
   std::vector<uint32_t> kb_arcs;
@@ -120,4 +123,11 @@ void launch_decode_trellis(const carmel_hip_decoder* d, bool lds, uint32_t n, co
 int decode_paths(carmel_hip_decoder* d, const char* who, uint32_t K, bool ranked, TrellisLaunch launch, uint64_t n_lines,
                  const uint64_t* off, const uint32_t* sym, uint64_t* line_paths, std::vector<double>& logw,
                  std::vector<uint64_t>& path_off, std::vector<uint32_t>& arcs);
+// What the path driver and the sampler make of a chunk's counting walk: np [n] paths a line (its first np[l] of K slots), len
+// and lw [n K] every slot's arcs and reported weight.  Appends the paths' weights to logw and their ends (from `base` on, the
+// arcs already held) to path_off, sets line_paths for the chunk's lines, -> [n K + 1]: where each slot's arcs go in the chunk's
+// compact path array (a slot without a path is empty).
+std::vector<uint64_t> decode_collect_paths(const DecodeChunk& c, uint32_t K, const std::vector<uint32_t>& np,
+                                           const std::vector<uint32_t>& len, const std::vector<double>& lw, uint64_t base,
+                                           uint64_t* line_paths, std::vector<double>& logw, std::vector<uint64_t>& path_off);
 }  // namespace carmel_hip

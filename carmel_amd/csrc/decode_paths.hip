@@ -1,6 +1,7 @@
-// decode_paths.hip — what the batch decoders' entry points run on (declared in decode.hpp): the chunk driver of all three
-// (carmel_hip_decode, carmel_hip_decode_kbest, carmel_hip_decode_sum), and for the two that return paths the walk kernel and the
-// path driver around it.
+// decode_paths.hip — what the batch decoders' entry points run on (declared in decode.hpp): the chunk driver of all four
+// (carmel_hip_decode, carmel_hip_decode_kbest, carmel_hip_decode_sum, carmel_hip_decode_sample), for the two that return the
+// paths of a path-recording trellis the walk kernel and the path driver around it, and the assembly of a chunk's paths that the
+// sampler (decode_sample.hip, a walk of its own) shares with that driver.
 //
 // The walk: a path-recording trellis leaves, per (position i, state q, rank r), the arc that enters the slot's path last and the
 // rank of that arc's source (DecodePaths).  One lane per (line, rank j) follows them from (n, final, j) to (0, start, 0), once to
@@ -123,6 +124,28 @@ int decode_chunks(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, 
   return CARMEL_HIP_OK;
 }
 
+std::vector<uint64_t> decode_collect_paths(const DecodeChunk& c, uint32_t K, const std::vector<uint32_t>& np,
+                                           const std::vector<uint32_t>& len, const std::vector<double>& lw, uint64_t base,
+                                           uint64_t* line_paths, std::vector<double>& logw, std::vector<uint64_t>& path_off) {
+  const uint32_t n = c.n;
+  // the slots of ranks a line does not have are empty paths: the arcs come back compact and in (line, rank) order
+  std::vector<uint64_t> h_poff((uint64_t)n * K + 1, 0);
+  for (uint32_t l = 0; l < n; ++l)
+    for (uint32_t j = 0; j < K; ++j) {
+      const uint64_t at = (uint64_t)l * K + j;
+      h_poff[at + 1] = h_poff[at] + (j < np[l] ? len[at] : 0);
+    }
+  for (uint32_t l = 0; l < n; ++l) {
+    for (uint32_t j = 0; j < np[l]; ++j) {
+      const uint64_t at = (uint64_t)l * K + j;
+      logw.push_back(lw[at]);
+      path_off.push_back(base + h_poff[at + 1]);
+    }
+    line_paths[c.lo + l + 1] = line_paths[c.lo + l] + np[l];
+  }
+  return h_poff;
+}
+
 int decode_paths(carmel_hip_decoder* d, const char* who, uint32_t K, bool ranked, TrellisLaunch launch, uint64_t n_lines,
                  const uint64_t* off, const uint32_t* sym, uint64_t* line_paths, std::vector<double>& logw,
                  std::vector<uint64_t>& path_off, std::vector<uint32_t>& arcs) {
@@ -176,24 +199,10 @@ int decode_paths(carmel_hip_decoder* d, const char* who, uint32_t K, bool ranked
     if (err & kErrCycle)  // kbest.h:160-166
       return fail(CARMEL_HIP_ERR_UNSUPPORTED, "best_path_has_cycle: the best path has a cycle (an epsilon cycle of weight > 1)");
     if (err) return fail(CARMEL_HIP_ERR_STATE, bad);
-    // the slots of ranks a line does not have are empty paths: the arcs come back compact and in (line, rank) order
-    std::vector<uint64_t> h_poff(n_slots + 1, 0);
-    for (uint32_t l = 0; l < n; ++l) {
+    for (uint32_t l = 0; l < n; ++l)
       if (np[l] > K) return fail(CARMEL_HIP_ERR_STATE, bad);
-      for (uint32_t j = 0; j < K; ++j) {
-        const uint64_t at = (uint64_t)l * K + j;
-        h_poff[at + 1] = h_poff[at] + (j < np[l] ? len[at] : 0);
-      }
-    }
     const uint64_t base = arcs.size();
-    for (uint32_t l = 0; l < n; ++l) {
-      for (uint32_t j = 0; j < np[l]; ++j) {
-        const uint64_t at = (uint64_t)l * K + j;
-        logw.push_back(lw[at]);
-        path_off.push_back(base + h_poff[at + 1]);
-      }
-      line_paths[c.lo + l + 1] = line_paths[c.lo + l] + np[l];
-    }
+    const std::vector<uint64_t> h_poff = decode_collect_paths(c, K, np, len, lw, base, line_paths, logw, path_off);
     if (!h_poff[n_slots]) return CARMEL_HIP_OK;
     HIPCHK(d_poff.upload(h_poff, s));
     HIPCHK(d_path.alloc(h_poff[n_slots]));

@@ -21,9 +21,9 @@
 // carmel.cc:1787): a cyclic one is refused before any launch.
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "decode_sum_node.hpp"
 #include "decode_trellis.hpp"
 #include "engine.hpp"
-#include "sweep_math.hpp"
 
 namespace {
 // the skeleton's node: one double a state
@@ -33,12 +33,7 @@ struct SumNode {
   __device__ void begin(uint32_t, int) {}
   __device__ void fill(const DecodeTables& T, uint32_t, uint32_t q, const double* prev, uint32_t m0, uint32_t m1, double* same,
                        uint32_t e0, uint32_t e1, bool start) const {
-    Lse a;
-    a.init();
-    if (start) a.add(0.0);
-    for (uint32_t k = m0; k < m1; ++k) a.add(prev[T.m_src[k]] + T.m_w[k]);
-    for (uint32_t k = e0; k < e1; ++k) a.add(same[T.e_src[k]] + T.e_w[k]);
-    same[q] = a.value();
+    same[q] = sum_node_value(T, prev, m0, m1, same, e0, e1, start);  // (decode_sum_node.hpp: shared with the sampler's forward pass)
   }
   __device__ void read_out(uint32_t line, const double* F) const { sum[line] = F[0]; }
 };

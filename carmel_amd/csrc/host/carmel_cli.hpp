@@ -97,6 +97,8 @@ struct Options {
   long kpaths = 0;  // -k n (carmel.cc:1021): best paths per line; only n = 1 with -b / -i (batch decoding, decode_batch)
   long kbest = 0;   // --kbest=N: N best paths per line (print_kbest(N, ...), carmel.cc:379-397), where -k 1 is accepted
   bool have_kbest = false;
+  long sample_paths = 0;  // --sample-paths=N: N derivations per line drawn from the posterior over the line's derivations
+  bool have_sample = false;  // (carmel_hip_decode_sample, seeded by -R); not carmel's -G, which generates from the whole machine
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };

@@ -5,6 +5,9 @@
 // per-line composition, which is never built, and is refused before this is reached.
 // --kbest=N prints, for every line, its N best derivations best first and then print_kbest's fill lines up to N
 // (carmel_hip_decode_kbest, csrc/decode_kbest.hip); the summary multiplies each line's first path, as with -k 1.
+// --sample-paths=N prints, for every line, N derivations drawn from the posterior over its derivations, in sample order
+// (carmel_hip_decode_sample, csrc/decode_sample.hip, seeded by -R), in the same format and with the same fill lines; no best path
+// is computed, so the report has no Viterbi line.  It is not carmel's -G, which generates from the whole machine.
 // --sum-paths (carmel's --sum) adds every line's sum of all paths (post_compose's sum_acyclic_paths, carmel.cc:555-599; carmel_hip_decode_sum,
 // csrc/decode_sum.hip) to the report on stderr; what goes to stdout does not change.
 #include <cctype>
@@ -71,8 +74,12 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   const size_t n = lines.size();
   line_paths.assign(n + 1, 0);
   const auto t0 = std::chrono::steady_clock::now();
-  if (o.have_kbest) {
-    hip_check(carmel_hip_decode_kbest(d, (uint32_t)kbest, n, off.data(), sym.data(), line_paths.data()), "carmel_hip_decode_kbest");
+  if (o.have_kbest || o.have_sample) {
+    if (o.have_sample)
+      hip_check(carmel_hip_decode_sample(d, (uint32_t)kbest, o.seed, n, off.data(), sym.data(), line_paths.data()),
+                "carmel_hip_decode_sample");
+    else
+      hip_check(carmel_hip_decode_kbest(d, (uint32_t)kbest, n, off.data(), sym.data(), line_paths.data()), "carmel_hip_decode_kbest");
     uint64_t n_paths = 0, n_path_arcs = 0;
     hip_check(carmel_hip_decoder_kbest_size(d, &n_paths, &n_path_arcs), "carmel_hip_decoder_kbest_size");
     best.resize(std::max<uint64_t>(n_paths, 1));
@@ -98,7 +105,8 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   if (timing_on()) {
     double kms = 0;
     carmel_hip_decoder_last_ms(d, &kms);
-    std::cerr << "timing: decode " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+    std::cerr << (o.have_sample ? "timing: sample " : "timing: decode ")
+              << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
               << " s (kernels " << kms * 1e-3 << " s)\n";
   }
 }
@@ -209,8 +217,10 @@ void Batch::report() const {
     std::cerr << "No derivations found for " << n_0prob << " of " << n << " inputs.\n";
   else
     std::cerr << "Derivations found for all " << n << " inputs.\n";
-  std::cerr << "Viterbi (best path) ";
-  log_ppx(n_prob, prod_viterbi, n_0prob);
+  if (!o.have_sample) {  // (sampling computes no best path)
+    std::cerr << "Viterbi (best path) ";
+    log_ppx(n_prob, prod_viterbi, n_0prob);
+  }
   if (o.sum) {
     std::cerr << "Sum (all paths) ";
     log_ppx(n_prob, prod_sum, n_0prob);
@@ -237,7 +247,7 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
     carmel_hip_decoder* d;
     ~Guard() { carmel_hip_decoder_destroy(d); }
   } guard{d};
-  const size_t kbest = o.have_kbest ? (size_t)o.kbest : 1;  // output lines per input line
+  const size_t kbest = o.have_sample ? (size_t)o.sample_paths : o.have_kbest ? (size_t)o.kbest : 1;  // output lines per input line
   b.decode(d, kbest);
   if (o.sum) b.sum_paths(d);
   b.print_paths(kbest, quiet);

@@ -28,6 +28,7 @@ static int print_help() {
                "--print-counts-to= --print-norms-from= --print-norms-to= --width= ... ; several GPUs: --gpus=N --exchange=; "
                "batch 1-best decoding: -b -i -s -r -k 1 with -I / -O / -@ (-Q -W -E); "
                "k-best decoding: --kbest=N (N <= 1024) in place of -k 1; "
+               "posterior path samples: --sample-paths=N (N <= 65536) in place of -k 1, seeded by -R (not carmel's -G; no epsilon cycles); "
                "all-paths sums in the decoding report: --sum-paths with -b / -i (carmel's --sum; no epsilon cycles); "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
@@ -35,9 +36,14 @@ static int print_help() {
 
 // batch decoding (-b / -i with -k 1): what is not implemented is refused here, before any device call; true: decoding
 static bool validate_decoding(const Options& o, bool with_pairs) {
-  const bool decoding = o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0 || o.have_kbest;
+  const bool decoding = o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0 || o.have_kbest || o.have_sample;
   if (decoding) {
-    if (o.have_kbest) {
+    if (o.have_sample) {
+      if (o.have_kbest) throw UsageError("--sample-paths=N and --kbest=N exclude each other");
+      if (o.sample_paths < 1 || o.sample_paths > 65536) throw UsageError("--sample-paths=N needs 1 <= N <= 65536");
+      if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.sample_paths) throw UsageError("--sample-paths=N with -k m: m must be 1 or N");
+      if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i']) throw UsageError("--sample-paths=N applies to batch decoding (-b or -i)");
+    } else if (o.have_kbest) {
       if (o.kbest < 1 || o.kbest > 1024) throw UsageError("--kbest=N needs 1 <= N <= 1024");
       if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.kbest) throw UsageError("--kbest=N with -k m: m must be 1 or N");
     } else {
@@ -53,7 +59,7 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
   } else if (o.flags[(unsigned)'s'] || o.flags[(unsigned)'r'])
     throw UsageError("-s / -r apply to batch decoding (-b or -i with -k 1)");
   else if (o.sum)
-    throw UsageError("--sum-paths applies to batch decoding (-b or -i with -k 1 or --kbest=N)");
+    throw UsageError("--sum-paths applies to batch decoding (-b or -i with -k 1, --kbest=N or --sample-paths=N)");
   return decoding;
 }
 

@@ -114,6 +114,10 @@ Options parse_args(int argc, char** argv) {
         o.kbest = std::atol(v.c_str());
         o.have_kbest = true;
       }
+      else if (k == "sample-paths") {  // not a carmel option: N posterior samples of every line's derivations (carmel_hip_decode_sample)
+        o.sample_paths = std::atol(v.c_str());
+        o.have_sample = true;
+      }
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")

@@ -1,15 +1,18 @@
-"""Batch 1-best and k-best decoding on the GPU (carmel -b -k n; include/carmel_hip.h carmel_hip_decoder_*, csrc/decode.hip and
-csrc/decode_kbest.hip, on the drivers of csrc/decode_paths.hip).
+"""Batch 1-best and k-best decoding, all-paths sums and posterior path samples on the GPU (carmel -b -k n; include/carmel_hip.h
+carmel_hip_decoder_*, csrc/decode.hip, csrc/decode_kbest.hip, csrc/decode_sum.hip and csrc/decode_sample.hip, on the drivers of
+csrc/decode_paths.hip).
 
     d = Decoder(wfst, side=0)          # side 0: lines are input strings; 1: output strings (carmel -r)
     best, paths = d.decode(lines)      # lines: sequences of symbol ids of that side's alphabet
     weights, kpaths = d.decode_kbest(lines, k)
     sums = d.sum(lines)                # ln of every line's sum over ALL its derivations (carmel -b --sum; csrc/decode_sum.hip)
+    weights, spaths = d.sample(lines, n, seed=0)   # n derivations per line, each drawn with probability weight / sum
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
 weights[l] holds the reported ln weights of line l's min(k, number of derivations) best derivations, best first, and kpaths[l]
-their arc ids; rank 0 is decode's path."""
+their arc ids; rank 0 is decode's path.  sample returns the same shapes: a line with a derivation has exactly n paths, in sample
+order, duplicates kept; sample s of line l depends on the machine, the line, the seed, l and s alone."""
 import ctypes as C
 
 import numpy as np
@@ -55,6 +58,17 @@ class Decoder(object):
         line_paths = np.zeros(len(lines) + 1, np.uint64)
         check(lib.carmel_hip_decode_kbest(self._h, int(k), len(lines), ptr(off), ptr(sym), ptr(line_paths)),
               "carmel_hip_decode_kbest")
+        return self._last_paths(line_paths)
+
+    def sample_raw(self, lines, n, seed=0):
+        """-> (line_paths, logw, path_off, arcs): the arrays of carmel_hip_decode_sample / carmel_hip_decoder_get_kbest"""
+        off, sym = _pack(lines)
+        line_paths = np.zeros(len(lines) + 1, np.uint64)
+        check(lib.carmel_hip_decode_sample(self._h, int(n), int(seed), len(lines), ptr(off), ptr(sym), ptr(line_paths)),
+              "carmel_hip_decode_sample")
+        return self._last_paths(line_paths)
+
+    def _last_paths(self, line_paths):
         n_paths, n_arcs = C.c_uint64(), C.c_uint64()
         check(lib.carmel_hip_decoder_kbest_size(self._h, C.byref(n_paths), C.byref(n_arcs)), "carmel_hip_decoder_kbest_size")
         assert n_paths.value == int(line_paths[-1])
@@ -65,9 +79,16 @@ class Decoder(object):
         return line_paths, logw[:n_paths.value], path_off, arcs[:n_arcs.value]
 
     def decode_kbest(self, lines, k):
-        line_paths, logw, path_off, arcs = self.decode_kbest_raw(lines, k)
+        return self._per_line(len(lines), *self.decode_kbest_raw(lines, k))
+
+    def sample(self, lines, n, seed=0):
+        """-> (weights, paths) shaped as decode_kbest's: per line its n sampled derivations (none: no derivation)"""
+        return self._per_line(len(lines), *self.sample_raw(lines, n, seed))
+
+    @staticmethod
+    def _per_line(n_lines, line_paths, logw, path_off, arcs):
         weights, paths = [], []
-        for l in range(len(lines)):
+        for l in range(n_lines):
             a, b = int(line_paths[l]), int(line_paths[l + 1])
             weights.append(logw[a:b].copy())
             paths.append([arcs[int(path_off[p]):int(path_off[p + 1])].copy() for p in range(a, b)])

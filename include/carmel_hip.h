@@ -544,7 +544,7 @@ int carmel_hip_decode(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* o
                       uint64_t* path_off);
 /* the last decode's paths: path_off[n_lines] arc ids, each line's in path order (wfst_paths_printer's arcs, fst.h:60-160) */
 int carmel_hip_decoder_get_paths(carmel_hip_decoder* d, uint32_t* arcs);
-/* the last decode's (1-best or k-best) kernel time (HIP events around the trellis and walk kernels, summed over chunks) */
+/* the last decode's (1-best, k-best, sum or sample) kernel time (HIP events around the trellis and walk kernels, summed over chunks) */
 int carmel_hip_decoder_last_ms(carmel_hip_decoder* d, double* kernel_ms);
 int carmel_hip_decoder_destroy(carmel_hip_decoder* d);
 
@@ -563,9 +563,9 @@ int carmel_hip_decoder_destroy(carmel_hip_decoder* d);
  * handle; carmel_hip_decoder_last_ms covers these kernels too. */
 int carmel_hip_decode_kbest(carmel_hip_decoder* d, uint32_t k, uint64_t n_lines, const uint64_t* off, const uint32_t* sym,
                             uint64_t* line_paths);
-/* the last k-best decode's sizes (fst.h:791 / carmel.cc:379-397: what print_kbest would visit): paths, and arcs of all paths */
+/* the last k-best or sample call's sizes (fst.h:791 / carmel.cc:379-397: what print_kbest would visit): paths, and arcs of all paths */
 int carmel_hip_decoder_kbest_size(carmel_hip_decoder* d, uint64_t* n_paths, uint64_t* n_arcs);
-/* the last k-best decode's paths (fst.h:791 / carmel.cc:379-397): path p has reported weight path_logw[p] and the arc ids
+/* the last k-best or sample call's paths (fst.h:791 / carmel.cc:379-397): path p has reported weight path_logw[p] and the arc ids
  * arcs[path_off[p] .. path_off[p + 1]) in path order; path_off has n_paths + 1 entries */
 int carmel_hip_decoder_get_kbest(carmel_hip_decoder* d, double* path_logw, uint64_t* path_off, uint32_t* arcs);
 
@@ -579,6 +579,25 @@ int carmel_hip_decoder_get_kbest(carmel_hip_decoder* d, double* path_logw, uint6
  * "acyclic-correct only", carmel.cc:1787).  May alternate with carmel_hip_decode and carmel_hip_decode_kbest on one handle, and
  * sees the weights of carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers this kernel too. */
 int carmel_hip_decode_sum(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, double* sum_logw);
+
+/* ---- batch posterior path sampling (csrc/decode_sample.hip) ----
+ * Stands beside carmel_hip_decode (the best derivation), carmel_hip_decode_kbest (the k best) and carmel_hip_decode_sum (the
+ * weight of all): for every line, n_samples derivations drawn independently with probability w(d) / (the sum over all
+ * derivations of the line), derivations as carmel_hip_decode_kbest defines them.  It replaces nothing of the reference: carmel's
+ * -G n (fst.h:708-757, carmel.cc:1446-1458) generates from the whole machine by locally normalised arc weights, retrying on dead
+ * ends, and is not this.  Lines as for carmel_hip_decode.  A line without a derivation gets no paths, every other line exactly
+ * n_samples -- paths line_paths[l] .. line_paths[l + 1] (line_paths: n_lines + 1 entries) of carmel_hip_decoder_kbest_size /
+ * carmel_hip_decoder_get_kbest -- in sample order, duplicates kept; a path's reported weight is its arcs' logs added from the
+ * END, as there.  The forward pass is carmel_hip_decode_sum's, bit for bit, with every row kept; sample s of line l walks back
+ * from the final node, choosing among the arcs into its node in proportion to exp(forward value of the source + arc weight -
+ * forward value of the node) with the draw carmel_hip_gibbs_uniform(seed, s, l, step) (DESIGN.md has the rule in full).  So a
+ * sample depends on the machine, the weights, the side, its line, the seed, l (the line's index in this call) and s alone: not
+ * on chunking, memory tier, launch order or the other lines.  1 <= n_samples <= 65536 and n_lines < 2^32, else
+ * CARMEL_HIP_ERR_ARG.  If the matched side's epsilon arcs have a cycle the call fails with CARMEL_HIP_ERR_UNSUPPORTED, naming the
+ * epsilon cycle, and nothing is written.  May alternate with carmel_hip_decode, carmel_hip_decode_kbest and carmel_hip_decode_sum
+ * on one handle, and sees the weights of carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers these kernels too. */
+int carmel_hip_decode_sample(carmel_hip_decoder* d, uint32_t n_samples, uint64_t seed, uint64_t n_lines, const uint64_t* off,
+                             const uint32_t* sym, uint64_t* line_paths);
 
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */

@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
-"""Batch 1-best and k-best decoding and all-paths sums on the MI355X (csrc/decode.hip, csrc/decode_kbest.hip,
-csrc/decode_sum.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
+"""Batch 1-best and k-best decoding, all-paths sums and posterior path samples on the MI355X (csrc/decode.hip,
+csrc/decode_kbest.hip, csrc/decode_sum.hip, csrc/decode_sample.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
 the output side as in `carmel -qbsriWIEk 1`) over tagging.data.noe repeated to about --lines lines, then the front end's
 end-to-end time for the tutorial's three decode commands.  Every --kbest K adds the same lines through carmel_hip_decode_kbest
 with that K ("kbest": kernel and call time, paths returned, and for K = 1 the ratio to the 1-best kernels' time of this run).
 --sum adds the same lines through carmel_hip_decode_sum, timed in the same run ("sum": kernel and call time, lines per second,
 the ratio to the 1-best kernels' time), and writes that run's figures to --sum-out (profiles/decode_sum_bench.json).
+Every --sample N adds the same lines through carmel_hip_decode_sample with N samples a line (seed 1), beside the sum and the
+1-best decode of the same run ("sample": kernel and call time, paths returned, the ratios to the sum's and the 1-best kernels'
+time), and writes that run's figures to --sample-out (profiles/decode_sample_bench.json).
 Prints one JSON object.
 
     python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...] [--sum]
+                                 [--sample 1 --sample 16]
 
 The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
 on the weights); the cluster and cipher commands use their committed trained members."""
@@ -45,6 +49,8 @@ def main():
     ap.add_argument("--kbest", type=int, action="append", default=[], metavar="K")
     ap.add_argument("--sum", action="store_true")
     ap.add_argument("--sum-out", default=os.path.join(ROOT, "profiles", "decode_sum_bench.json"))
+    ap.add_argument("--sample", type=int, action="append", default=[], metavar="N")
+    ap.add_argument("--sample-out", default=os.path.join(ROOT, "profiles", "decode_sample_bench.json"))
     a = ap.parse_args()
     from carmel_amd.decode import Decoder
     from carmel_amd.model import Wfst
@@ -79,7 +85,7 @@ def main():
                          "rank0_equals_1best": bool(np.array_equal(logw[line_paths[:-1][np.diff(line_paths) > 0].astype(np.int64)],
                                                                    best[~np.isneginf(best)]))}
     sums = None
-    if a.sum:
+    if a.sum or a.sample:  # (the samples are reported beside the sum of the same run)
         d.sum(lines[:1000])
         kms_s, wall_s = [], []
         for _ in range(a.reps):
@@ -92,6 +98,21 @@ def main():
                 "sum_ln": float(total[~np.isneginf(total)].sum()), "viterbi_ln": float(best[~np.isneginf(best)].sum()),
                 # (a line with one derivation sums its arcs in path order, the 1-best weight is added from the end: the last bit may differ)
                 "max_1best_minus_sum": float(np.max(best[~np.isneginf(best)] - total[~np.isneginf(best)]))}
+    samples = {}
+    for N in a.sample:
+        d.sample_raw(lines[:1000], N, 1)
+        kms_n, wall_n = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            line_paths, logw, path_off, arcs = d.sample_raw(lines, N, 1)
+            wall_n.append((time.perf_counter() - t0) * 1e3)
+            kms_n.append(d.last_ms())
+        with_paths = np.diff(line_paths) > 0
+        samples[str(N)] = {"kernel_ms": float(np.median(kms_n)), "kernel_ms_all": kms_n, "call_ms": float(np.median(wall_n)),
+                           "paths": int(len(logw)), "path_arcs": int(len(arcs)),
+                           "lines_per_s": len(lines) / (float(np.median(kms_n)) * 1e-3),
+                           "every_line_with_a_sum_has_n_paths": bool(np.array_equal(with_paths, ~np.isneginf(total)) and
+                                                                     (np.diff(line_paths)[with_paths] == N).all())}
     d.close()
     n_pos = int(sum(len(x) for x in lines))
     # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
@@ -123,6 +144,17 @@ def main():
     if sums:
         sums["kernel_ms_over_1best"] = sums["kernel_ms"] / kms
         res["sum"] = sums
+    if samples:
+        for v in samples.values():
+            v["kernel_ms_over_sum"] = v["kernel_ms"] / sums["kernel_ms"]
+            v["kernel_ms_over_1best"] = v["kernel_ms"] / kms
+        res["sample"] = samples
+        with open(a.sample_out, "w") as f:
+            json.dump({"workload": res["workload"], "machine": res["machine"], "reps": a.reps,
+                       "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
+                                    "lines_per_s": res["lines_per_s"]}, "sum": sums, "sample": samples}, f)
+            f.write("\n")
+    if a.sum:
         with open(a.sum_out, "w") as f:
             json.dump({"workload": res["workload"], "machine": res["machine"], "reps": a.reps,
                        "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
