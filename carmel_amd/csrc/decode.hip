@@ -10,6 +10,8 @@
 //     (0 without one), an arc filed under the level of its destination.  If the epsilon subgraph has a cycle there are no
 //     levels: the closure relaxes every epsilon arc in arc-id order, round after round, to a fixed point (at most |Q| rounds).
 //   Arcs of weight zero are dropped here: they are never taken.
+//   * the same arcs filed under their SOURCES (DecodeOutTables, for the backward pass of decode_posterior.hip): matched arcs by
+//     (symbol, src, arc id), one segment per source; epsilon arcs by (level of src, src, arc id), one entry per source.
 //
 // Per line (one wavefront = one workgroup of 64 lanes per line; lines launched longest first):
 //   d_0 = 0 at the start state (0), -inf elsewhere, closed over the epsilon arcs;
@@ -238,6 +240,51 @@ int carmel_hip_decoder::upload_tables() {
   for (uint64_t k = 0; k < n_arcs; ++k) h_aeps[k] = msym[k] == 0;
   std::vector<uint8_t> h_epsin(Q, 0);
   for (uint32_t k : eps) h_epsin[dst[k]] = 1;
+  // the outgoing view (DecodeOutTables): matched arcs by (symbol, src, arc id), one segment per (symbol, src); epsilon arcs by
+  // (level of src, src, arc id), one entry per source -- the same arcs, the same levels
+  std::vector<uint32_t> omatched(matched), oeps;
+  std::sort(omatched.begin(), omatched.end(), [&](uint32_t a, uint32_t b) {
+    return msym[a] != msym[b] ? msym[a] < msym[b] : src[a] != src[b] ? src[a] < src[b] : a < b;
+  });
+  std::vector<uint32_t> h_osym_seg(n_syms + 1, 0), h_oseg_src, h_oseg_arc, h_omdst, h_omid;
+  std::vector<double> h_omw;
+  for (size_t j = 0; j < omatched.size(); ++j) {
+    const uint32_t k = omatched[j];
+    if (j == 0 || msym[k] != msym[omatched[j - 1]] || src[k] != src[omatched[j - 1]]) {
+      h_oseg_src.push_back(src[k]);
+      h_oseg_arc.push_back((uint32_t)j);
+      h_osym_seg[msym[k] + 1]++;
+    }
+    h_omdst.push_back(dst[k]);
+    h_omw.push_back(logw[k]);
+    h_omid.push_back(k);
+  }
+  h_oseg_arc.push_back((uint32_t)omatched.size());
+  for (uint32_t x = 0; x < n_syms; ++x) h_osym_seg[x + 1] += h_osym_seg[x];
+  std::vector<uint32_t> h_olvl_ent(n_levels + 1, 0), h_oent_src, h_oent_arc, h_oedst, h_oeid, h_ostent(Q, kNone);
+  std::vector<double> h_oew;
+  std::vector<uint8_t> h_epsout(Q, 0);
+  if (!eps_cyclic) {
+    oeps = eps;
+    std::sort(oeps.begin(), oeps.end(), [&](uint32_t a, uint32_t b) {
+      return level[src[a]] != level[src[b]] ? level[src[a]] < level[src[b]] : src[a] != src[b] ? src[a] < src[b] : a < b;
+    });
+  }
+  for (size_t j = 0; j < oeps.size(); ++j) {
+    const uint32_t k = oeps[j];
+    if (j == 0 || src[k] != src[oeps[j - 1]]) {
+      h_ostent[src[k]] = (uint32_t)h_oent_src.size();
+      h_oent_src.push_back(src[k]);
+      h_oent_arc.push_back((uint32_t)j);
+      h_olvl_ent[level[src[k]] + 1]++;  // (a source's level is below its destinations': at most n_levels - 1)
+    }
+    h_oedst.push_back(dst[k]);
+    h_oew.push_back(logw[k]);
+    h_oeid.push_back(k);
+    h_epsout[src[k]] = 1;
+  }
+  h_oent_arc.push_back((uint32_t)oeps.size());
+  for (uint32_t L = 0; L < n_levels; ++L) h_olvl_ent[L + 1] += h_olvl_ent[L];
   hipStream_t s = stream;
   HIPCHK(sym_seg.upload(h_sym_seg, s));
   HIPCHK(seg_dst.upload(h_seg_dst, s));
@@ -257,7 +304,23 @@ int carmel_hip_decoder::upload_tables() {
   HIPCHK(a_eps.upload(h_aeps, s));
   HIPCHK(eps_in.upload(h_epsin, s));
   HIPCHK(st_ent.upload(h_stent, s));
+  HIPCHK(o_sym_seg.upload(h_osym_seg, s));
+  HIPCHK(o_seg_src.upload(h_oseg_src, s));
+  HIPCHK(o_seg_arc.upload(h_oseg_arc, s));
+  HIPCHK(o_m_dst.upload(h_omdst, s));
+  HIPCHK(o_m_w.upload(h_omw, s));
+  HIPCHK(o_m_id.upload(h_omid, s));
+  HIPCHK(o_lvl_ent.upload(h_olvl_ent, s));
+  HIPCHK(o_ent_src.upload(h_oent_src, s));
+  HIPCHK(o_ent_arc.upload(h_oent_arc, s));
+  HIPCHK(o_e_dst.upload(h_oedst, s));
+  HIPCHK(o_e_w.upload(h_oew, s));
+  HIPCHK(o_e_id.upload(h_oeid, s));
+  HIPCHK(eps_out.upload(h_epsout, s));
+  HIPCHK(o_st_ent.upload(h_ostent, s));
   HIPCHK(hipStreamSynchronize(s));
+  TO = DecodeOutTables{o_sym_seg.p, o_seg_src.p, o_seg_arc.p, o_m_dst.p, o_m_w.p,  o_m_id.p,  o_lvl_ent.p,
+                       o_ent_src.p, o_ent_arc.p, o_e_dst.p,   o_e_w.p,   o_e_id.p, eps_out.p, o_st_ent.p};
   T = DecodeTables{Q, final_state, n_syms, sym_seg.p, seg_dst.p, seg_arc.p, m_src.p, m_w.p, m_id.p, n_levels, eps_cyclic ? 1 : 0,
                    lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size(), st_ent.p};
   return CARMEL_HIP_OK;

@@ -1,9 +1,9 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
-// samples decode_sample.hip) share: the prepared tables, the decoder handle, the constants, the arguments every trellis kernel
-// takes, and the host drivers of decode_paths.hip -- the chunk driver of all four entry points, the path driver of the two that
-// return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables
-// are built and uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum
-// share is decode_trellis.hpp.
+// samples decode_sample.hip, arc posteriors decode_posterior.hip) share: the prepared tables, the decoder handle, the constants,
+// the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all five entry points,
+// the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built and
+// uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum share is
+// decode_trellis.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -38,6 +38,27 @@ struct DecodeTables {
   const uint32_t* st_ent;    // [n_states] -> the entry whose destination the state is (kNone: no epsilon arc enters it, or cyclic)
 };
 
+// The outgoing view of the same arcs, for the backward pass of the arc posteriors (decode_posterior.hip): DecodeTables files an arc
+// under its destination, this under its source.  Symbols, dropped arcs and epsilon levels are DecodeTables'; a source's level is
+// strictly lower than the levels of its epsilon arcs' destinations, so the levels that hold sources are 0 .. n_levels - 1.
+// Empty epsilon lists when the epsilon subgraph is cyclic (no levels: the posteriors are refused).
+struct DecodeOutTables {
+  const uint32_t* sym_seg;   // [n_syms + 1] -> segments
+  const uint32_t* seg_src;   // [n_seg]
+  const uint32_t* seg_arc;   // [n_seg + 1] -> matched arcs
+  const uint32_t* m_dst;     // matched arcs, by (symbol, src, arc id)
+  const double* m_w;
+  const uint32_t* m_id;
+  const uint32_t* lvl_ent;   // [n_levels + 1] -> entries (one source state each), by the level of the source
+  const uint32_t* ent_src;
+  const uint32_t* ent_arc;   // [n_ent + 1] -> epsilon arcs
+  const uint32_t* e_dst;     // epsilon arcs, by (level of src, src, arc id)
+  const double* e_w;
+  const uint32_t* e_id;
+  const uint8_t* eps_out;    // [n_states]: an epsilon arc leaves the state
+  const uint32_t* st_ent;    // [n_states] -> the entry whose source the state is (kNone: no epsilon arc leaves it)
+};
+
 // a chunk's lines, as every trellis kernel takes them: one workgroup of kLanes lanes per line
 struct DecodeLines {
   const uint64_t* off;    // chunk-local CSR of the lines' symbols
@@ -70,6 +91,12 @@ struct carmel_hip_decoder {
   DevBuf<uint8_t> a_eps;
   DevBuf<uint8_t> eps_in;  // [|Q|]: the state is the destination of an epsilon arc of non-zero weight (k-best: its epsilon level is >= 1)
   DecodeTables T;
+  // the outgoing view (DecodeOutTables), and the arc counts of a carmel_hip_decode_posterior call: zeroed once per call,
+  // accumulated over all its chunks
+  DevBuf<uint32_t> o_sym_seg, o_seg_src, o_seg_arc, o_m_dst, o_m_id, o_lvl_ent, o_ent_src, o_ent_arc, o_e_dst, o_e_id, o_st_ent;
+  DevBuf<double> o_m_w, o_e_w, count;
+  DevBuf<uint8_t> eps_out;
+  DecodeOutTables TO;
   std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
   // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample): every path's reported weight, the CSR
   // of the paths' arcs, the arcs

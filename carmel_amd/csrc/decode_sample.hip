@@ -31,7 +31,7 @@
 #include <cstring>
 #include <limits>
 #include <vector>
-#include "decode_sum_node.hpp"
+#include "decode_sample_node.hpp"
 #include "decode_trellis.hpp"
 #include "engine.hpp"
 #include "rng.hpp"
@@ -39,26 +39,8 @@
 namespace {
 constexpr uint32_t kMaxSamples = 65536;
 
-// the skeleton's node: the sum's, and every node's value kept for the walk
-struct SampleNode {
-  const uint64_t* a_off;  // [n + 1]: each line's (len + 1) x |Q| doubles
-  double* alpha;
-  uint32_t* has;  // [n]: the line has a derivation
-  __host__ __device__ uint32_t width() const { return 1; }
-  __device__ void begin(uint32_t line, int lane) {
-    const uint64_t n = a_off[line + 1] - a_off[line];
-    alpha += a_off[line];
-    for (uint64_t s = lane; s < n; s += kLanes) alpha[s] = s == 0 ? 0.0 : -std::numeric_limits<double>::infinity();  // (0, start): 0.0
-  }
-  __device__ void fill(const DecodeTables& T, uint32_t pos, uint32_t q, const double* prev, uint32_t m0, uint32_t m1, double* same,
-                       uint32_t e0, uint32_t e1, bool start) const {
-    const double v = sum_node_value(T, prev, m0, m1, same, e0, e1, start);
-    same[q] = v;
-    alpha[(size_t)pos * T.n_states + q] = v;
-  }
-  __device__ void read_out(uint32_t line, const double* F) const { has[line] = F[0] > -std::numeric_limits<double>::infinity(); }
-};
-
+// (the skeleton's node, SampleNode -- the sum's, and every node's value kept for the walk -- is decode_sample_node.hpp's, shared
+// with decode_posterior.hip)
 // what the walk kernel takes beside the tables and the lines
 struct SampleWalk {
   uint32_t n_lines, n_samples;

@@ -1,5 +1,5 @@
 // decode_sum_node.hpp — the log-semiring value of one trellis node, shared by the all-paths sum (decode_sum.hip: SumNode) and the
-// posterior sampler's forward pass (decode_sample.hip: SampleNode), so that the two agree bit for bit: ONE streaming accumulator
+// forward pass that keeps every row (decode_sample_node.hpp: SampleNode, the sampler's and the arc posteriors'), so that they agree bit for bit: ONE streaming accumulator
 // (sweep_math.hpp's Lse), fed 0.0 first at node (0, start) only, then the matched candidates prev[src] + w of the arcs [m0, m1)
 // in arc-id order, then the epsilon candidates same[src] + w of the arcs [e0, e1) in arc-id order, and read out once.  A
 // candidate of -inf adds nothing; a node that nothing reaches is -inf.  (decode_sum.hip's header says what this order fixes.)

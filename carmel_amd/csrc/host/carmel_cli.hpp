@@ -99,6 +99,8 @@ struct Options {
   bool have_kbest = false;
   long sample_paths = 0;  // --sample-paths=N: N derivations per line drawn from the posterior over the line's derivations
   bool have_sample = false;  // (carmel_hip_decode_sample, seeded by -R); not carmel's -G, which generates from the whole machine
+  std::string posterior_counts;  // --posterior-counts=FILE: the composed machine with every arc's expected count over all derivations
+  bool have_posterior = false;   // of the lines as its weight (carmel_hip_decode_posterior), written to FILE
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };

@@ -10,6 +10,10 @@
 // is computed, so the report has no Viterbi line.  It is not carmel's -G, which generates from the whole machine.
 // --sum-paths (carmel's --sum) adds every line's sum of all paths (post_compose's sum_acyclic_paths, carmel.cc:555-599; carmel_hip_decode_sum,
 // csrc/decode_sum.hip) to the report on stderr; what goes to stdout does not change.
+// --posterior-counts=FILE writes the composed machine to FILE as Transducer::to_text does (-H / -J apply), every arc's weight
+// replaced by its expected number of uses over all derivations of the lines, every line weighing 1 (carmel_hip_decode_posterior,
+// csrc/decode_posterior.hip: the E-step of carmel -t for these lines); every arc is written, one never used with weight 0.
+// Nothing on stdout or stderr changes.
 #include <cctype>
 #include "carmel_cli.hpp"
 using namespace carmel_host;
@@ -38,6 +42,7 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   int read_lines(const std::string& text, bool side_out);
   void decode(carmel_hip_decoder* d, size_t kbest);
   void sum_paths(carmel_hip_decoder* d);
+  void posterior_counts(carmel_hip_decoder* d) const;
   void format_path(uint64_t p, std::string& buf) const;
   void print_paths(size_t kbest, bool quiet);
   void log_ppx(double n_pairs, double prod, size_t n_0) const;
@@ -128,6 +133,27 @@ void Batch::sum_paths(carmel_hip_decoder* d) {
       ++pre_n_prob;
       prod_sum += sums[l];
     }
+}
+
+// every arc's expected count over the derivations of all lines, as the weights of a copy of the machine, into the file
+void Batch::posterior_counts(carmel_hip_decoder* d) const {
+  std::vector<double> count(std::max<size_t>(M.num_arcs(), 1));
+  const auto t0 = std::chrono::steady_clock::now();
+  hip_check(carmel_hip_decode_posterior(d, lines.size(), off.data(), sym.data(), nullptr, nullptr, count.data()),
+            "carmel_hip_decode_posterior");
+  if (timing_on()) {
+    double kms = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    std::cerr << "timing: posterior " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+              << " s (kernels " << kms * 1e-3 << " s)\n";
+  }
+  for (double& c : count) c = c > 0 ? std::log(c) : kNegInf;
+  Transducer counted(M);
+  counted.set_weights(count.data());
+  std::ofstream of(o.posterior_counts.c_str());
+  of << counted.to_text(o.flags[(unsigned)'J'], o.flags[(unsigned)'H'], ws, /*include_zero=*/true);
+  of.close();
+  if (!of) throw std::runtime_error("--posterior-counts: cannot write " + o.posterior_counts);
 }
 
 // one path of a line into buf, as path_print writes it
@@ -250,6 +276,7 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
   const size_t kbest = o.have_sample ? (size_t)o.sample_paths : o.have_kbest ? (size_t)o.kbest : 1;  // output lines per input line
   b.decode(d, kbest);
   if (o.sum) b.sum_paths(d);
+  if (o.have_posterior) b.posterior_counts(d);
   b.print_paths(kbest, quiet);
   b.report();
   return 0;

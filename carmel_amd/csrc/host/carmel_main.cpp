@@ -30,6 +30,8 @@ static int print_help() {
                "k-best decoding: --kbest=N (N <= 1024) in place of -k 1; "
                "posterior path samples: --sample-paths=N (N <= 65536) in place of -k 1, seeded by -R (not carmel's -G; no epsilon cycles); "
                "all-paths sums in the decoding report: --sum-paths with -b / -i (carmel's --sum; no epsilon cycles); "
+               "arc posteriors: --posterior-counts=FILE with -b / -i writes the composed machine with every arc's expected count "
+               "over all derivations of the lines as its weight (no epsilon cycles); "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -37,6 +39,12 @@ static int print_help() {
 // batch decoding (-b / -i with -k 1): what is not implemented is refused here, before any device call; true: decoding
 static bool validate_decoding(const Options& o, bool with_pairs) {
   const bool decoding = o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0 || o.have_kbest || o.have_sample;
+  if (o.have_posterior) {
+    if (o.posterior_counts.empty()) throw UsageError("--posterior-counts=FILE needs a file name");
+    if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i'])
+      throw UsageError("--posterior-counts=FILE applies to batch decoding (-b or -i)");
+    if (with_pairs) throw UsageError("--posterior-counts=FILE with -t / --train-cascade / -S is not implemented");
+  }
   if (decoding) {
     if (o.have_sample) {
       if (o.have_kbest) throw UsageError("--sample-paths=N and --kbest=N exclude each other");

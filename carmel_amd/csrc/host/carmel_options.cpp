@@ -118,6 +118,10 @@ Options parse_args(int argc, char** argv) {
         o.sample_paths = std::atol(v.c_str());
         o.have_sample = true;
       }
+      else if (k == "posterior-counts") {  // not a carmel option: every arc's expected count over the lines (carmel_hip_decode_posterior)
+        o.posterior_counts = v;
+        o.have_posterior = true;
+      }
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")

@@ -1,18 +1,22 @@
-"""Batch 1-best and k-best decoding, all-paths sums and posterior path samples on the GPU (carmel -b -k n; include/carmel_hip.h
-carmel_hip_decoder_*, csrc/decode.hip, csrc/decode_kbest.hip, csrc/decode_sum.hip and csrc/decode_sample.hip, on the drivers of
-csrc/decode_paths.hip).
+"""Batch 1-best and k-best decoding, all-paths sums, posterior path samples and arc posteriors on the GPU (carmel -b -k n;
+include/carmel_hip.h carmel_hip_decoder_*, csrc/decode.hip, csrc/decode_kbest.hip, csrc/decode_sum.hip, csrc/decode_sample.hip
+and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
 
     d = Decoder(wfst, side=0)          # side 0: lines are input strings; 1: output strings (carmel -r)
     best, paths = d.decode(lines)      # lines: sequences of symbol ids of that side's alphabet
     weights, kpaths = d.decode_kbest(lines, k)
     sums = d.sum(lines)                # ln of every line's sum over ALL its derivations (carmel -b --sum; csrc/decode_sum.hip)
     weights, spaths = d.sample(lines, n, seed=0)   # n derivations per line, each drawn with probability weight / sum
+    sums, counts = d.posterior(lines, weights=None)   # expected uses of every arc over all derivations of the lines
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
 weights[l] holds the reported ln weights of line l's min(k, number of derivations) best derivations, best first, and kpaths[l]
 their arc ids; rank 0 is decode's path.  sample returns the same shapes: a line with a derivation has exactly n paths, in sample
-order, duplicates kept; sample s of line l depends on the machine, the line, the seed, l and s alone."""
+order, duplicates kept; sample s of line l depends on the machine, the line, the seed, l and s alone.  posterior returns sum's
+sums, bit for bit, and counts[a] = the sum over the lines with a derivation of weights[l] (1 without weights) times the expected
+number of uses of arc a over line l's derivations, each derivation weighing weight / sum (csrc/decode_posterior.hip: forward and
+backward trellis); the sums are fixed to the bit, the counts up to the order of the device's atomic adds."""
 import ctypes as C
 
 import numpy as np
@@ -100,6 +104,18 @@ class Decoder(object):
         out = np.empty(len(lines))
         check(lib.carmel_hip_decode_sum(self._h, len(lines), ptr(off), ptr(sym), ptr(out)), "carmel_hip_decode_sum")
         return out
+
+    def posterior(self, lines, weights=None):
+        """-> (sums, counts): sum(lines), and per arc its expected number of uses over the derivations of the lines (line l counts
+        weights[l] times, 1 without weights; weights are finite and >= 0); a line without a derivation adds nothing"""
+        off, sym = _pack(lines)
+        sums = np.empty(len(lines))
+        counts = np.zeros(max(self.n_arcs, 1))
+        wt = None if weights is None else f64(weights)
+        assert wt is None or len(wt) == len(lines)
+        check(lib.carmel_hip_decode_posterior(self._h, len(lines), ptr(off), ptr(sym), ptr(wt), ptr(sums), ptr(counts)),
+              "carmel_hip_decode_posterior")
+        return sums, counts[:self.n_arcs]
 
     def last_ms(self):
         ms = C.c_double()

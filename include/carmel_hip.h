@@ -599,6 +599,25 @@ int carmel_hip_decode_sum(carmel_hip_decoder* d, uint64_t n_lines, const uint64_
 int carmel_hip_decode_sample(carmel_hip_decoder* d, uint32_t n_samples, uint64_t seed, uint64_t n_lines, const uint64_t* off,
                              const uint32_t* sym, uint64_t* line_paths);
 
+/* ---- batch arc posteriors (csrc/decode_posterior.hip) ----
+ * Stands in for: the forward/backward of carmel -t (train.cc:254-266, 698-860: the E-step's expected arc counts), stated for
+ * one-sided lines against a machine that is composed once, where the reference builds a derivation lattice per pair.  Lines as
+ * for carmel_hip_decode; derivations as carmel_hip_decode_kbest defines them.  arc_count[a] (n_arcs entries, overwritten) is the
+ * sum over the lines l that have a derivation of line_weight[l] (1 if line_weight is null) times the expected number of uses of arc
+ * a over the derivations of l, each weighted by w(d) / (the sum over all derivations of l); a line without a derivation adds
+ * nothing, an arc of weight zero has count 0.  sum_logw (n_lines entries, may be null) gets every line's sum of all paths, bit for
+ * bit carmel_hip_decode_sum's, -inf = no derivation, whatever the line's weight.  The forward pass is carmel_hip_decode_sample's
+ * with every row kept; the backward pass feeds every node's accumulator in one fixed order and adds every trellis edge's posterior
+ * exp((forward value of the source + arc weight) + backward value of the destination - the line's sum) to its arc with an atomic
+ * add (DESIGN.md has the rule in full): sum_logw is fixed to the bit, arc_count up to the order of those adds.  A line weight that
+ * is negative or not finite, a null d, off or arc_count, or bad offsets: CARMEL_HIP_ERR_ARG; a weight of 0 is legal.  If the matched
+ * side's epsilon arcs have a cycle the call fails with CARMEL_HIP_ERR_UNSUPPORTED, naming the epsilon cycle, and nothing is
+ * written.  May alternate with the other four entry points on one handle, and sees the weights of
+ * carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers both kernels. */
+int carmel_hip_decode_posterior(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym,
+                                const double* line_weight /* nullable */, double* sum_logw /* [n_lines], nullable */,
+                                double* arc_count /* [n_arcs], overwritten */);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;

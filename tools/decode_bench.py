@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Batch 1-best and k-best decoding, all-paths sums and posterior path samples on the MI355X (csrc/decode.hip,
-csrc/decode_kbest.hip, csrc/decode_sum.hip, csrc/decode_sample.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
+"""Batch 1-best and k-best decoding, all-paths sums, posterior path samples and arc posteriors on the MI355X (csrc/decode.hip,
+csrc/decode_kbest.hip, csrc/decode_sum.hip, csrc/decode_sample.hip, csrc/decode_posterior.hip): the tagging machine (tagging.fsa.trained.noe o tagging.fst, words on
 the output side as in `carmel -qbsriWIEk 1`) over tagging.data.noe repeated to about --lines lines, then the front end's
 end-to-end time for the tutorial's three decode commands.  Every --kbest K adds the same lines through carmel_hip_decode_kbest
 with that K ("kbest": kernel and call time, paths returned, and for K = 1 the ratio to the 1-best kernels' time of this run).
@@ -9,10 +9,14 @@ the ratio to the 1-best kernels' time), and writes that run's figures to --sum-o
 Every --sample N adds the same lines through carmel_hip_decode_sample with N samples a line (seed 1), beside the sum and the
 1-best decode of the same run ("sample": kernel and call time, paths returned, the ratios to the sum's and the 1-best kernels'
 time), and writes that run's figures to --sample-out (profiles/decode_sample_bench.json).
+--posterior adds the same lines through carmel_hip_decode_posterior, beside the sum and --sample 1 of the same run ("posterior":
+kernel and call time, lines per second, the ratios to the sum's, the one-sample and the 1-best kernels' time, the total of the
+matched arcs' counts against the positions of the lines with a derivation), and writes that run's figures to --posterior-out
+(profiles/decode_posterior_bench.json).
 Prints one JSON object.
 
     python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...] [--sum]
-                                 [--sample 1 --sample 16]
+                                 [--sample 1 --sample 16] [--posterior]
 
 The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
 on the weights); the cluster and cipher commands use their committed trained members."""
@@ -51,7 +55,10 @@ def main():
     ap.add_argument("--sum-out", default=os.path.join(ROOT, "profiles", "decode_sum_bench.json"))
     ap.add_argument("--sample", type=int, action="append", default=[], metavar="N")
     ap.add_argument("--sample-out", default=os.path.join(ROOT, "profiles", "decode_sample_bench.json"))
+    ap.add_argument("--posterior", action="store_true")
+    ap.add_argument("--posterior-out", default=os.path.join(ROOT, "profiles", "decode_posterior_bench.json"))
     a = ap.parse_args()
+    sample_ns = a.sample + ([1] if a.posterior and 1 not in a.sample else [])  # (the posteriors are reported beside one sample a line)
     from carmel_amd.decode import Decoder
     from carmel_amd.model import Wfst
     from decode_ref import golden_file
@@ -85,7 +92,7 @@ def main():
                          "rank0_equals_1best": bool(np.array_equal(logw[line_paths[:-1][np.diff(line_paths) > 0].astype(np.int64)],
                                                                    best[~np.isneginf(best)]))}
     sums = None
-    if a.sum or a.sample:  # (the samples are reported beside the sum of the same run)
+    if a.sum or sample_ns:  # (the samples and the posteriors are reported beside the sum of the same run)
         d.sum(lines[:1000])
         kms_s, wall_s = [], []
         for _ in range(a.reps):
@@ -99,7 +106,7 @@ def main():
                 # (a line with one derivation sums its arcs in path order, the 1-best weight is added from the end: the last bit may differ)
                 "max_1best_minus_sum": float(np.max(best[~np.isneginf(best)] - total[~np.isneginf(best)]))}
     samples = {}
-    for N in a.sample:
+    for N in sample_ns:
         d.sample_raw(lines[:1000], N, 1)
         kms_n, wall_n = [], []
         for _ in range(a.reps):
@@ -113,6 +120,21 @@ def main():
                            "lines_per_s": len(lines) / (float(np.median(kms_n)) * 1e-3),
                            "every_line_with_a_sum_has_n_paths": bool(np.array_equal(with_paths, ~np.isneginf(total)) and
                                                                      (np.diff(line_paths)[with_paths] == N).all())}
+    post = None
+    if a.posterior:
+        d.posterior(lines[:1000])
+        kms_p, wall_p = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            psums, counts = d.posterior(lines)
+            wall_p.append((time.perf_counter() - t0) * 1e3)
+            kms_p.append(d.last_ms())
+        has = ~np.isneginf(psums)
+        post = {"kernel_ms": float(np.median(kms_p)), "kernel_ms_all": kms_p, "call_ms": float(np.median(wall_p)),
+                "lines_per_s": len(lines) / (float(np.median(kms_p)) * 1e-3),
+                "sums_equal_the_sum": bool(psums.tobytes() == total.tobytes()),
+                "matched_count": float(counts[w["osym"] != 0].sum()),
+                "positions_with_a_derivation": int(sum(len(x) for x, h in zip(lines, has) if h))}
     d.close()
     n_pos = int(sum(len(x) for x in lines))
     # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
@@ -149,10 +171,21 @@ def main():
             v["kernel_ms_over_sum"] = v["kernel_ms"] / sums["kernel_ms"]
             v["kernel_ms_over_1best"] = v["kernel_ms"] / kms
         res["sample"] = samples
+    if a.sample:
         with open(a.sample_out, "w") as f:
             json.dump({"workload": res["workload"], "machine": res["machine"], "reps": a.reps,
                        "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
                                     "lines_per_s": res["lines_per_s"]}, "sum": sums, "sample": samples}, f)
+            f.write("\n")
+    if post:
+        post["kernel_ms_over_sum"] = post["kernel_ms"] / sums["kernel_ms"]
+        post["kernel_ms_over_sample_1"] = post["kernel_ms"] / samples["1"]["kernel_ms"]
+        post["kernel_ms_over_1best"] = post["kernel_ms"] / kms
+        res["posterior"] = post
+        with open(a.posterior_out, "w") as f:
+            json.dump({"workload": res["workload"], "machine": res["machine"], "reps": a.reps,
+                       "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
+                                    "lines_per_s": res["lines_per_s"]}, "sum": sums, "sample_1": samples["1"], "posterior": post}, f)
             f.write("\n")
     if a.sum:
         with open(a.sum_out, "w") as f:
