@@ -32,12 +32,20 @@ namespace carmel_hip {
 // at most the in-degree.  The library's log spends most of its ~80 instructions on arguments that cannot occur here (denormals,
 // zero, negatives, infinities); this one is a frexp, one division and an odd series in s = (m - 1) / (m + 1), m in
 // [sqrt(1/2), sqrt(2)): ln m = 2 s (1 + z/3 + z^2/5 + ... + z^10/21), z = s^2 <= 0.0295 (the first dropped term is below 2^-60
-// of the sum).  A third of the instructions; within 2 ulp of the library's (tests/test_gpu_parity.py compares every sweep with the
-// oracle's libm arithmetic).  On the ambiguous workloads the log per state was what the lane sweeps' arithmetic was made of.
+// of the sum).  A third of the instructions.  Within 2.5 ulp of the EXACT logarithm (measured: 2.0 ulp at worst, next to 1, where
+// s2 and s2 z p round separately; 1.3 on [2, 4096], 0.54 above 2^32) and exactly 0 at 1.  On the ambiguous workloads the log per
+// state was what the lane sweeps' arithmetic was made of.
 // e^x for the arguments the sweeps have: differences to a running maximum and log-posteriors (x <= 0 up to rounding), -inf for
 // dead arcs and padding.  Cody-Waite reduction by ln 2, Taylor to r^13 on |r| <= ln2 / 2 (remainder below 2^-57), ldexp -- which
 // also carries arguments below -745 through the denormals to 0; no branches for overflow or NaN inputs, which cannot occur.
-__device__ __forceinline__ double exp_le0(double x) {
+// Within 1 ulp of the EXACT exponential on [-745.2, 40] (measured: 0.91 ulp at worst; the Horner steps' roundings, not the
+// series), denormal results included; exactly 1 at +-0 and exactly 0 from -745.2 down.
+// Both functions and Lse are __host__ __device__ so that tests/native/sweep_math_probe.hip can evaluate them on the CPU:
+// tests/test_sweep_math_host.py holds host evaluation to these bounds against an 80-bit reference and Lse to
+// (4 n + 4) u + u |value|, tests/test_sweep_math_gpu.py holds the device to the same bounds and to the host's bits in both ways
+// this header is compiled (default contraction, -ffp-contract=off), and tests/test_sweep_f80_gpu.py every sweep built on them to
+// a tolerance derived from these figures (profiles/measurement_log_sweep_math.md, measurement_log_sweep_f80.md).
+__host__ __device__ __forceinline__ double exp_le0(double x) {
   x = fmax(x, -1100.0);  // (-inf included; 2^-1587 is 0 through ldexp)
   const double n = rint(x * 1.44269504088896340736);
   double r = fma(n, -6.93147180369123816490e-01, x);
@@ -58,7 +66,7 @@ __device__ __forceinline__ double exp_le0(double x) {
   p = fma(p, r, 1.0);
   return ldexp(p, (int)n);
 }
-__device__ __forceinline__ double log_ge1(double a) {
+__host__ __device__ __forceinline__ double log_ge1(double a) {
   int e;
   double m = frexp(a, &e);  // [0.5, 1)
   const bool lo = m < 0.70710678118654752440;
@@ -84,11 +92,11 @@ __device__ __forceinline__ double log_ge1(double a) {
 }
 struct Lse {
   double m, acc;
-  __device__ __forceinline__ void init() {
+  __host__ __device__ __forceinline__ void init() {
     m = NEG_INF;
     acc = 0.0;
   }
-  __device__ __forceinline__ void add(double x) {
+  __host__ __device__ __forceinline__ void add(double x) {
     if (x == NEG_INF) return;
     if (x <= m) {
       acc += K_EXP(x - m);
@@ -97,7 +105,7 @@ struct Lse {
       m = x;
     }
   }
-  __device__ __forceinline__ double value() const { return acc == 1.0 ? m : (acc > 0.0 ? m + K_LOG(acc) : NEG_INF); }
+  __host__ __device__ __forceinline__ double value() const { return acc == 1.0 ? m : (acc > 0.0 ? m + K_LOG(acc) : NEG_INF); }
 };
 
 // ---------------- blocked transposition (TransBucket, lattice.hpp) ----------------

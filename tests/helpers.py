@@ -89,17 +89,18 @@ def host_lattices(w, c, prune=True, threads=2, small_pairs=0, small_states=0, la
     return out
 
 
-def _lse(xs):
-    xs = np.asarray(xs, dtype=np.float64)
+def _lse(xs, dtype=np.float64):
+    xs = np.asarray(xs, dtype=dtype)
     if len(xs) == 0:
-        return -np.inf
+        return dtype(-np.inf)
     m = xs.max()
     if m == -np.inf:
-        return -np.inf
+        return dtype(-np.inf)
     return m + np.log(np.exp(xs - m).sum())
 
 
-def _lwadd(a, b):
+def _lwadd(a, b, dtype=np.float64):
+    a, b = dtype(a), dtype(b)
     if a == -np.inf:
         return b
     if b == -np.inf:
@@ -112,15 +113,86 @@ def _lwadd(a, b):
     return (b + np.log1p(np.exp(d))) if d < 0 else (a + np.log1p(np.exp(-d)))
 
 
+_LSE, _LWADD = _lse, _lwadd  # (numpy_sweep wraps the two under their own names)
+
+
+class SweepStats(object):
+    """what numpy_sweep saw, for a tolerance computed from the run itself (sweep_ref.py).  A chain is one pass over one
+    lattice (or bundle of lattices): its dependent sums one after the other -- the levels, or the states of a lane lattice one
+    by one, or the pairwise adds of a cyclic lattice.  L = the longest chain, D = the largest sum over a chain of the most
+    terms any sum of a step has, A = the largest finite |ln alpha|, |ln beta|, |term| or |ln p| stored, N = the largest
+    number of posteriors summed into one arc, cyclic = the most pairwise adds in one pass over a cyclic lattice"""
+
+    def __init__(self, n_arcs):
+        self.L, self.D, self.A, self.cyclic = 0, 0, 0.0, 0
+        self.uses = np.zeros(n_arcs, np.int64)
+        self._d, self._sum, self._n = 0, 0, 0
+
+    @property
+    def N(self):
+        return int(self.uses.max()) if len(self.uses) else 0
+
+    def next_step(self):
+        """the sums seen since the last call were one step of the chain"""
+        self._sum += self._d
+        self._n += 1
+        self._d = 0
+
+    def end_chain(self, cyclic=False):
+        if self._d:
+            self.next_step()
+        self.L, self.D = max(self.L, self._n), max(self.D, self._sum)
+        if cyclic:
+            self.cyclic = max(self.cyclic, self._n)
+        self._sum = self._n = 0
+
+    def seen(self, terms, value=None):
+        """the terms of one sum (or one value)"""
+        t = np.asarray(terms, np.longdouble).ravel()
+        self._d = max(self._d, len(t))
+        for v in (t, np.asarray([] if value is None else [value], np.longdouble)):
+            v = v[np.isfinite(v)]
+            if len(v):
+                self.A = max(self.A, float(np.abs(v).max()))
+
+
+class _NoStats(SweepStats):
+    """numpy_sweep without a SweepStats: nothing is recorded"""
+
+    def next_step(self):
+        pass
+
+    def end_chain(self, cyclic=False):
+        pass
+
+    def seen(self, terms, value=None):
+        pass
+
+
 def alpha_s(col, s):
     return col[s]
 
 
-def numpy_sweep(img, logw, n_pairs_total):
+def numpy_sweep(img, logw, n_pairs_total, dtype=np.float64, stats=None):
     """forward / backward / counts over the bundle image exactly as kernels.hip walks it.
-    Returns (counts linear per WFST arc, per-pair ln prob)."""
-    counts = np.zeros(len(logw))
-    plp = np.full(n_pairs_total, -np.inf)
+    Returns (counts linear per WFST arc, per-pair ln prob).  dtype: the type of everything computed -- the weights, every
+    alpha and beta, the sums, the posteriors, the counts and ln p (np.longdouble: the f80 restatement of sweep_ref.py; the
+    image's ln pair weights are the doubles the kernels read, widened).  stats: a SweepStats to fill."""
+    logw = np.asarray(logw, dtype)
+    counts = np.zeros(len(logw), dtype)
+    plp = np.full(n_pairs_total, -np.inf, dtype)
+    sst = stats if stats is not None else _NoStats(len(logw))
+
+    def _lse(xs):
+        v = _LSE(xs, dtype)
+        sst.seen(xs, v)
+        return v
+
+    def _lwadd(a, b):
+        v = _LWADD(a, b, dtype)
+        sst.seen([a, b], v)
+        sst.next_step()
+        return v
     # lane groups: the per-lane record streams exactly as sweep_lane_kernel consumes them
     for g in img.get("lane_groups", []):
         base, ml = int(g["stream_base"]), int(g["maxlen"])
@@ -134,8 +206,8 @@ def numpy_sweep(img, logw, n_pairs_total):
             if win:
                 assert win & (win - 1) == 0 and int(g["max_states"]) == win
             wm = rows - 1 if win else 0xffffffff
-            col = np.full(rows, np.nan)
-            spill = np.full(S, np.nan)
+            col = np.full(rows, np.nan, dtype)
+            spill = np.full(S, np.nan, dtype)
             col[0] = spill[0] = 0.0
             d, terms, wcache = 1, [], {}
             for k in range(ml):
@@ -150,11 +222,15 @@ def numpy_sweep(img, logw, n_pairs_total):
                 wcache[bpos] = (arc, logw[arc])
                 if x & LANE_LAST:
                     col[d & wm] = spill[d] = _lse(terms)
+                    sst.next_step()
                     d, terms = d + 1, []
             assert d == S and not terms
+            sst.end_chain()
             lp = col[(S - 1) & wm]
             plp[img["lane_pair"][slot]] = lp
-            col[(S - 1) & wm] = img["lane_logw"][slot] - lp
+            col[(S - 1) & wm] = dtype(img["lane_logw"][slot]) - lp
+            sst.seen([lp], col[(S - 1) & wm])
+            sst.next_step()
             s, terms = S - 2, []
             for k in range(ml):
                 x, arc = img["lane_bwd"][base + k * 64 + l]
@@ -165,10 +241,13 @@ def numpy_sweep(img, logw, n_pairs_total):
                 assert wcache[k][0] == arc  # the forward pass left this arc's weight at exactly this position
                 t = wcache[k][1] + col[dst & wm]
                 counts[arc] += np.exp(spill[(x >> 10) & 0x3ff] + t)
+                sst.uses[arc] += 1
                 terms.append(t)
                 if x & LANE_LAST:
                     col[s & wm] = _lse(terms)
+                    sst.next_step()
                     s, terms = s - 1, []
+            sst.end_chain()
             assert s == -1 and not terms
     # one-per-wavefront lattices: rows of 64 records per level, exactly as sweep_wave_kernel consumes them (WaveDesc)
     wv = img.get("waves")
@@ -187,7 +266,7 @@ def numpy_sweep(img, logw, n_pairs_total):
 
         class Ring(object):
             def __init__(self):
-                self.a = np.full(ring if ring else S, np.nan)
+                self.a = np.full(ring if ring else S, np.nan, dtype)
                 self.owner = np.full(ring if ring else S, -1)
 
             def __getitem__(self, s):
@@ -199,7 +278,7 @@ def numpy_sweep(img, logw, n_pairs_total):
                 k = s % ring if ring else s
                 self.a[k], self.owner[k] = v, s
         val = Ring()
-        spill = np.full(S, np.nan)
+        spill = np.full(S, np.nan, dtype)
         val[0] = spill[0] = 0.0
         n_valid = 0
         for l in range(1, NL):
@@ -219,10 +298,14 @@ def numpy_sweep(img, logw, n_pairs_total):
             assert sorted(terms) == list(range(lvl[l + 1] - lvl[l]))  # every state of the level has an in-arc
             for dr, ts in terms.items():
                 val[lvl[l] + dr] = spill[lvl[l] + dr] = _lse(ts)
+            sst.next_step()
+        sst.end_chain()
         assert n_valid == int(d["n_arcs"])
         lp = val[S - 1]
         plp[int(d["pair"])] = lp
-        val[S - 1] = float(d["logw"]) - lp
+        val[S - 1] = dtype(d["logw"]) - lp
+        sst.seen([lp], val[S - 1])
+        sst.next_step()
         n_valid = 0
         for k in range(1, NL):
             l = NL - 1 - k
@@ -240,11 +323,14 @@ def numpy_sweep(img, logw, n_pairs_total):
                     arc = int(wv["bwd_arc"][pos])
                     t = logw[arc] + val[dst]
                     counts[arc] += np.exp(spill[lvl[l] + sr] + t)
+                    sst.uses[arc] += 1
                     terms.setdefault(sr, []).append(t)
                     n_valid += 1
             assert sorted(terms) == list(range(lvl[l + 1] - lvl[l]))
             for sr, ts in terms.items():
                 val[lvl[l] + sr] = _lse(ts)
+            sst.next_step()
+        sst.end_chain()
         assert n_valid == int(d["n_arcs"])
     for b in img["bundles"]:
         ns = int(b["n_states"])
@@ -255,8 +341,8 @@ def numpy_sweep(img, logw, n_pairs_total):
         oa = img["out_arcs"][ab:ab + int(b["n_arcs"])]
         lv = img["level_off"][int(b["level_base"]):int(b["level_base"]) + int(b["n_levels"]) + 1]
         pb, npb = int(b["pair_base"]), int(b["n_pairs"])
-        alpha = np.full(ns, -np.inf)
-        beta = np.full(ns, -np.inf)
+        alpha = np.full(ns, -np.inf, dtype)
+        beta = np.full(ns, -np.inf, dtype)
         if b["flags"] & 1:  # cyclic: the reference's in-order scatter sweeps
             st, fin = int(img["pair_start"][pb]), int(img["pair_final"][pb])
             alpha[st] = 0.0
@@ -264,6 +350,7 @@ def numpy_sweep(img, logw, n_pairs_total):
                 for a in range(ioff[0] * 0 + ooff[s], ooff[s + 1]):
                     d, arc = oa[a]
                     alpha[d] = _lwadd(alpha[d], alpha[s] + logw[arc])
+            sst.end_chain(cyclic=True)
             prob = alpha[fin]
             plp[img["pair_id"][pb]] = prob
             beta[fin] = 0.0
@@ -271,10 +358,12 @@ def numpy_sweep(img, logw, n_pairs_total):
                 for a in range(ioff[s], ioff[s + 1]):
                     u, arc = ia[a]
                     beta[u] = _lwadd(beta[u], beta[s] + logw[arc])
+            sst.end_chain(cyclic=True)
             for s in range(ns):
                 for a in range(ooff[s], ooff[s + 1]):
                     d, arc = oa[a]
-                    counts[arc] += np.exp(logw[arc] + alpha[s] + beta[d] + img["pair_logw"][pb] - prob)
+                    counts[arc] += np.exp(logw[arc] + alpha[s] + beta[d] + dtype(img["pair_logw"][pb]) - prob)
+                    sst.uses[arc] += 1
             continue
         for p in range(npb):
             alpha[img["pair_start"][pb + p]] = 0.0
@@ -283,10 +372,14 @@ def numpy_sweep(img, logw, n_pairs_total):
                 r = ia[ioff[s]:ioff[s + 1]]
                 assert np.all(r[:, 0] < lv[l]), "in-arc source must lie in an earlier level"
                 alpha[s] = _lse(alpha[r[:, 0]] + logw[r[:, 1]])
+            sst.next_step()
+        sst.end_chain()
         for p in range(npb):
             f = img["pair_final"][pb + p]
             plp[img["pair_id"][pb + p]] = alpha[f]
-            beta[f] = img["pair_logw"][pb + p] - alpha[f]
+            beta[f] = dtype(img["pair_logw"][pb + p]) - alpha[f]
+            sst.seen([alpha[f]], beta[f])
+        sst.next_step()
         for l in range(int(b["n_levels"]) - 1, -1, -1):
             for s in range(lv[l], lv[l + 1]):
                 r = oa[ooff[s]:ooff[s + 1]]
@@ -296,6 +389,9 @@ def numpy_sweep(img, logw, n_pairs_total):
                 t = logw[r[:, 1]] + beta[r[:, 0]]
                 beta[s] = _lse(t)
                 np.add.at(counts, r[:, 1], np.exp(alpha[s] + t))
+                np.add.at(sst.uses, r[:, 1], 1)
+            sst.next_step()
+        sst.end_chain()
     return counts, plp
 
 
