@@ -10,6 +10,8 @@
 //     (0 without one), an arc filed under the level of its destination.  If the epsilon subgraph has a cycle there are no
 //     levels: the closure relaxes every epsilon arc in arc-id order, round after round, to a fixed point (at most |Q| rounds).
 //   Arcs of weight zero are dropped here: they are never taken.
+//   * for the pair decoder (decode_pairs.hip, DecodePairTables): the other side's symbol of every arc, and the epsilon arcs by the
+//     levels of the subgraph of the arcs with epsilon on BOTH sides, which exist also when the levels above do not;
 //   * the same arcs filed under their SOURCES (DecodeOutTables, for the backward pass of decode_posterior.hip): matched arcs by
 //     (symbol, src, arc id), one segment per source; epsilon arcs by (level of src, src, arc id), one entry per source.
 //
@@ -285,7 +287,79 @@ int carmel_hip_decoder::upload_tables() {
   }
   h_oent_arc.push_back((uint32_t)oeps.size());
   for (uint32_t L = 0; L < n_levels; ++L) h_olvl_ent[L + 1] += h_olvl_ent[L];
+  // the pair decoder's tables (DecodePairTables): the other side's symbols, and the epsilon arcs by the levels of the 00 subgraph
+  // alone (Kahn again, over the arcs with epsilon on both sides); from the epsilon arcs in arc-id order, never from the levels above
+  std::vector<uint32_t> h_mosym, peps, plevel(Q, 0), pindeg(Q, 0), h_plvl_ent, h_pent_dst, h_pent_arc, h_pesrc, h_peid, h_peosym;
+  std::vector<double> h_pew;
+  for (uint32_t k : matched) h_mosym.push_back(osym[k]);
+  uint32_t max_seg = 0;
+  for (uint32_t x = 0; x < n_syms; ++x) max_seg = std::max(max_seg, h_sym_seg[x + 1] - h_sym_seg[x]);
+  for (uint64_t k = 0; k < n_arcs; ++k)
+    if (logw[k] > ninf && msym[k] == 0) peps.push_back((uint32_t)k);
+  std::vector<std::vector<uint32_t> > pouts(Q);
+  for (uint32_t k : peps)
+    if (osym[k] == 0) {
+      pouts[src[k]].push_back(k);
+      pindeg[dst[k]]++;
+    }
+  work.clear();
+  for (uint32_t q = 0; q < Q; ++q)
+    if (!pindeg[q]) work.push_back(q);
+  pair_levels = 0;
+  for (seen = 0; seen < work.size();) {
+    const uint32_t q = work[seen++];
+    for (uint32_t k : pouts[q]) {
+      plevel[dst[k]] = std::max(plevel[dst[k]], plevel[q] + 1);
+      pair_levels = std::max(pair_levels, plevel[dst[k]]);
+      if (--pindeg[dst[k]] == 0) work.push_back(dst[k]);
+    }
+  }
+  pair_cycle.clear();
+  if (seen < Q) {  // name one cycle: from a state Kahn left, step to a predecessor it left too until a state repeats
+    std::vector<uint32_t> pred(Q, kNone), mark(Q, kNone);
+    for (uint32_t k : peps)
+      if (osym[k] == 0 && pindeg[src[k]] && pindeg[dst[k]] && pred[dst[k]] == kNone) pred[dst[k]] = src[k];
+    uint32_t q = 0;
+    while (!pindeg[q]) ++q;
+    uint32_t step = 0;
+    for (; mark[q] == kNone; q = pred[q]) mark[q] = step++;
+    std::string names = std::to_string(q);
+    for (uint32_t r = pred[q]; r != q; r = pred[r]) names = std::to_string(r) + " -> " + names;
+    pair_cycle = "states " + std::to_string(q) + " -> " + names;
+    pair_levels = 0;
+  } else {
+    std::stable_sort(peps.begin(), peps.end(), [&](uint32_t a, uint32_t b) {
+      return plevel[dst[a]] != plevel[dst[b]] ? plevel[dst[a]] < plevel[dst[b]] : dst[a] < dst[b];
+    });
+    h_plvl_ent.assign(peps.empty() ? 1 : pair_levels + 2, 0);
+    for (size_t j = 0; j < peps.size(); ++j) {
+      const uint32_t k = peps[j];
+      if (j == 0 || dst[k] != dst[peps[j - 1]]) {
+        h_pent_dst.push_back(dst[k]);
+        h_pent_arc.push_back((uint32_t)j);
+        h_plvl_ent[plevel[dst[k]] + 1]++;
+      }
+      h_pesrc.push_back(src[k]);
+      h_pew.push_back(logw[k]);
+      h_peid.push_back(k);
+      h_peosym.push_back(osym[k]);
+    }
+    h_pent_arc.push_back((uint32_t)peps.size());
+    for (size_t L = 0; L + 1 < h_plvl_ent.size(); ++L) h_plvl_ent[L + 1] += h_plvl_ent[L];
+  }
+  if (h_plvl_ent.empty()) h_plvl_ent.assign(1, 0);
+  std::vector<uint8_t> h_aflags(n_arcs);
+  for (uint64_t k = 0; k < n_arcs; ++k) h_aflags[k] = (msym[k] != 0 ? 1 : 0) | (osym[k] != 0 ? 2 : 0);
   hipStream_t s = stream;
+  HIPCHK(p_m_osym.upload(h_mosym, s));
+  HIPCHK(p_lvl_ent.upload(h_plvl_ent, s));
+  HIPCHK(p_ent_dst.upload(h_pent_dst, s));
+  HIPCHK(p_ent_arc.upload(h_pent_arc, s));
+  HIPCHK(p_e_src.upload(h_pesrc, s));
+  HIPCHK(p_e_w.upload(h_pew, s));
+  HIPCHK(p_e_id.upload(h_peid, s));
+  HIPCHK(p_e_osym.upload(h_peosym, s));
+  HIPCHK(a_flags.upload(h_aflags, s));
   HIPCHK(sym_seg.upload(h_sym_seg, s));
   HIPCHK(seg_dst.upload(h_seg_dst, s));
   HIPCHK(seg_arc.upload(h_seg_arc, s));
@@ -321,6 +395,8 @@ int carmel_hip_decoder::upload_tables() {
   HIPCHK(hipStreamSynchronize(s));
   TO = DecodeOutTables{o_sym_seg.p, o_seg_src.p, o_seg_arc.p, o_m_dst.p, o_m_w.p,  o_m_id.p,  o_lvl_ent.p,
                        o_ent_src.p, o_ent_arc.p, o_e_dst.p,   o_e_w.p,   o_e_id.p, eps_out.p, o_st_ent.p};
+  TP = DecodePairTables{p_m_osym.p, (uint32_t)h_plvl_ent.size() - 1, max_seg, p_lvl_ent.p, p_ent_dst.p, p_ent_arc.p, p_e_src.p,
+                        p_e_w.p,    p_e_id.p, p_e_osym.p};
   T = DecodeTables{Q, final_state, n_syms, sym_seg.p, seg_dst.p, seg_arc.p, m_src.p, m_w.p, m_id.p, n_levels, eps_cyclic ? 1 : 0,
                    lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size(), st_ent.p};
   return CARMEL_HIP_OK;
@@ -349,6 +425,7 @@ int carmel_hip_decoder_create(carmel_hip_decoder** out, int device, uint32_t n_s
   d->src.assign(src, src + n_arcs);
   d->dst.assign(dst, dst + n_arcs);
   d->msym.assign(side ? out_sym : in_sym, (side ? out_sym : in_sym) + n_arcs);  // -r: the machine inverted
+  d->osym.assign(side ? in_sym : out_sym, (side ? in_sym : out_sym) + n_arcs);
   d->logw.assign(logw, logw + n_arcs);
   HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
   HIPCHK(hipEventCreate(&d->ev0));

@@ -1,6 +1,6 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
-// samples decode_sample.hip, arc posteriors decode_posterior.hip) share: the prepared tables, the decoder handle, the constants,
-// the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all five entry points,
+// samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip) share: the prepared tables, the decoder
+// handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built and
 // uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum share is
 // decode_trellis.hpp.
@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <functional>
+#include <string>
 #include <vector>
 #include "engine.hpp"
 
@@ -59,6 +60,24 @@ struct DecodeOutTables {
   const uint32_t* st_ent;    // [n_states] -> the entry whose source the state is (kNone: no epsilon arc leaves it)
 };
 
+// What the pair decoder (decode_pairs.hip) adds to DecodeTables' matched arrays: the other side's symbol of every matched arc, and
+// the matched-side-epsilon arcs once more, ordered for a trellis over (matched position i, other position j, state q).  There an
+// epsilon arc whose other symbol is not epsilon (0M) advances j and needs no order inside a cell; only the arcs with epsilon on
+// both sides (00) do, so the levels are the longest-path levels of the 00 subgraph ALONE: they exist whenever the 00 arcs are
+// acyclic, also when DecodeTables' epsilon levels do not (a 0M self-loop).  A state that only 0M arcs enter is at level 0.
+struct DecodePairTables {
+  const uint32_t* m_osym;   // parallel to m_src / m_w / m_id
+  uint32_t n_levels;        // 1 + the highest 00 level of a state that an epsilon arc enters (0: no epsilon arcs)
+  uint32_t max_seg;         // the most destination segments a matched symbol has
+  const uint32_t* lvl_ent;  // [n_levels + 1] -> entries (one destination state each), by the 00 level of the state
+  const uint32_t* ent_dst;
+  const uint32_t* ent_arc;  // [n_ent + 1] -> epsilon arcs
+  const uint32_t* e_src;    // epsilon arcs, by (00 level of dst, dst, arc id)
+  const double* e_w;
+  const uint32_t* e_id;
+  const uint32_t* e_osym;   // 0: a 00 arc (source in the same cell); else a 0M arc (source in cell (i, j - 1))
+};
+
 // a chunk's lines, as every trellis kernel takes them: one workgroup of kLanes lanes per line
 struct DecodeLines {
   const uint64_t* off;    // chunk-local CSR of the lines' symbols
@@ -97,6 +116,14 @@ struct carmel_hip_decoder {
   DevBuf<double> o_m_w, o_e_w, count;
   DevBuf<uint8_t> eps_out;
   DecodeOutTables TO;
+  // the pair decoder's tables (decode_pairs.hip); pair_cycle: empty, or the 00 cycle that makes both pair entry points refuse
+  std::vector<uint32_t> osym;  // the other side's symbol of every arc
+  DevBuf<uint32_t> p_m_osym, p_lvl_ent, p_ent_dst, p_ent_arc, p_e_src, p_e_id, p_e_osym;
+  DevBuf<double> p_e_w;
+  DevBuf<uint8_t> a_flags;  // per arc, for the pair walk: bit 0 the matched symbol is not epsilon, bit 1 the other symbol is not
+  DecodePairTables TP;
+  uint32_t pair_levels = 0;  // the highest 00 level
+  std::string pair_cycle;
   std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
   // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample): every path's reported weight, the CSR
   // of the paths' arcs, the arcs
@@ -123,6 +150,9 @@ struct DecodeChunk {
   uint32_t n;             // hi - lo
   const uint64_t* h_off;  // [n + 1]: L.off on the host
   DecodeLines L;          // on the device
+  const uint64_t* h_off2;  // pairs: the second lines' chunk-local CSR on the host, and (off2, sym2) on the device
+  const uint64_t* off2;
+  const uint32_t* sym2;
   bool lds;               // the rows are in LDS
   float ms;
   int begin();
@@ -138,6 +168,15 @@ int decode_check_lines(const char* who, uint64_t n_lines, const uint64_t* off);
 // lines are uploaded with their launch order (longest first) and handed to `body`; d->last_ms is set if every chunk returns 0.
 int decode_chunks(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, uint64_t a, uint64_t b,
                   uint64_t cap, uint64_t row_doubles, const std::function<int(DecodeChunk&)>& body);
+
+// The same driver with the cost of a line given by its index (cost(l) bytes, whatever it is made of): chunks of fewer than `cap`
+// lines whose costs fit the budget, a line that costs more goes alone; a chunk's launch order is costliest first (stable).  With
+// off2 / sym2 (pairs) the second lines of the chunk are uploaded beside the first.  The driver allocates no rows: c.L.rows is
+// nullptr, c.lds is `lds`.  decode_chunks above is this with cost(l) = a len + b (+ 16 row_doubles in the global tier), which
+// orders by length as it always did, and with its rows.
+int decode_chunks_by_cost(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, const uint64_t* off2,
+                          const uint32_t* sym2, bool lds, const std::function<uint64_t(uint64_t)>& cost, uint64_t cap,
+                          const std::function<int(DecodeChunk&)>& body);
 
 // launches a path-recording trellis kernel over the n lines of a chunk
 typedef void (*TrellisLaunch)(const carmel_hip_decoder* d, bool lds, uint32_t n, const DecodeLines& L, const DecodePaths& P,

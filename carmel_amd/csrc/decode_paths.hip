@@ -1,5 +1,6 @@
-// decode_paths.hip — what the batch decoders' entry points run on (declared in decode.hpp): the chunk driver of all five
-// (carmel_hip_decode, carmel_hip_decode_kbest, carmel_hip_decode_sum, carmel_hip_decode_sample, carmel_hip_decode_posterior), for
+// decode_paths.hip — what the batch decoders' entry points run on (declared in decode.hpp): the chunk driver of all of them
+// (carmel_hip_decode, carmel_hip_decode_kbest, carmel_hip_decode_sum, carmel_hip_decode_sample, carmel_hip_decode_posterior by a
+// line's length; carmel_hip_decode_pairs and carmel_hip_decode_pairs_sum by a pair's cost), for
 // the two that return the
 // paths of a path-recording trellis the walk kernel and the path driver around it, and the assembly of a chunk's paths that the
 // sampler (decode_sample.hip, a walk of its own) shares with that driver.
@@ -88,41 +89,65 @@ int decode_check_lines(const char* who, uint64_t n_lines, const uint64_t* off) {
   return CARMEL_HIP_OK;
 }
 
-int decode_chunks(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, uint64_t a, uint64_t b,
-                  uint64_t cap, uint64_t row_doubles, const std::function<int(DecodeChunk&)>& body) {
+int decode_chunks_by_cost(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, const uint64_t* off2,
+                          const uint32_t* sym2, bool lds, const std::function<uint64_t(uint64_t)>& cost, uint64_t cap,
+                          const std::function<int(DecodeChunk&)>& body) {
   HIPCHK(hipSetDevice(d->device));
   hipStream_t s = d->stream;
   DecodeChunk c{d};
-  c.lds = row_doubles <= kLdsStates && !lib_opt_off("decode_lds");
+  c.lds = lds;
   c.ms = 0;
   uint64_t budget = 1ull << 30;
   if (const char* v = lib_opt("decode_chunk_bytes")) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
-  auto line_bytes = [&](uint64_t l) { return (off[l + 1] - off[l]) * a + b + (c.lds ? 0 : 16ull * row_doubles); };
-  DevBuf<uint64_t> d_off;
-  DevBuf<uint32_t> d_sym, d_order;
-  DevBuf<double> d_rows;
+  DevBuf<uint64_t> d_off, d_off2;
+  DevBuf<uint32_t> d_sym, d_sym2, d_order;
   for (c.lo = 0; c.lo < n_lines; c.lo = c.hi) {
-    uint64_t bytes = line_bytes(c.lo);
+    uint64_t bytes = cost(c.lo);
     c.hi = c.lo + 1;
-    while (c.hi < n_lines && c.hi - c.lo < cap && bytes + line_bytes(c.hi) <= budget) bytes += line_bytes(c.hi++);
+    while (c.hi < n_lines && c.hi - c.lo < cap && bytes + cost(c.hi) <= budget) bytes += cost(c.hi++);
     c.n = (uint32_t)(c.hi - c.lo);
-    std::vector<uint64_t> h_off(c.n + 1);
+    std::vector<uint64_t> h_off(c.n + 1), h_off2, h_cost(c.n);
     for (uint32_t l = 0; l <= c.n; ++l) h_off[l] = off[c.lo + l] - off[c.lo];
+    for (uint32_t l = 0; l < c.n; ++l) h_cost[l] = cost(c.lo + l);
     std::vector<uint32_t> order(c.n);
     std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t x, uint32_t y) { return h_off[x + 1] - h_off[x] > h_off[y + 1] - h_off[y]; });
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return h_cost[x] > h_cost[y]; });
     HIPCHK(d_off.upload(h_off, s));
     const std::vector<uint32_t> h_sym(sym + off[c.lo], sym + off[c.hi]);  // (named: the copy is asynchronous)
     HIPCHK(d_sym.upload(h_sym, s));
     HIPCHK(d_order.upload(order, s));
-    if (!c.lds) HIPCHK(d_rows.alloc((size_t)c.n * 2 * row_doubles));
+    std::vector<uint32_t> h_sym2;
+    if (off2) {
+      h_off2.resize(c.n + 1);
+      for (uint32_t l = 0; l <= c.n; ++l) h_off2[l] = off2[c.lo + l] - off2[c.lo];
+      h_sym2.assign(sym2 + off2[c.lo], sym2 + off2[c.hi]);
+      HIPCHK(d_off2.upload(h_off2, s));
+      HIPCHK(d_sym2.upload(h_sym2, s));
+    }
     c.h_off = h_off.data();
-    c.L = DecodeLines{d_off.p, d_sym.p, d_order.p, c.lds ? nullptr : d_rows.p};
+    c.h_off2 = off2 ? h_off2.data() : nullptr;
+    c.off2 = d_off2.p;
+    c.sym2 = d_sym2.p;
+    c.L = DecodeLines{d_off.p, d_sym.p, d_order.p, nullptr};
     if (const int rc = body(c)) return rc;
   }
   d->last_ms = c.ms;
   return CARMEL_HIP_OK;
+}
+
+int decode_chunks(carmel_hip_decoder* d, uint64_t n_lines, const uint64_t* off, const uint32_t* sym, uint64_t a, uint64_t b,
+                  uint64_t cap, uint64_t row_doubles, const std::function<int(DecodeChunk&)>& body) {
+  const bool lds = row_doubles <= kLdsStates && !lib_opt_off("decode_lds");
+  DevBuf<double> d_rows;
+  return decode_chunks_by_cost(
+      d, n_lines, off, sym, nullptr, nullptr, lds,
+      [&](uint64_t l) { return (off[l + 1] - off[l]) * a + b + (lds ? 0 : 16ull * row_doubles); }, cap, [&](DecodeChunk& c) {
+        if (!lds) {
+          HIPCHK(d_rows.alloc((size_t)c.n * 2 * row_doubles));
+          c.L.rows = d_rows.p;
+        }
+        return body(c);
+      });
 }
 
 std::vector<uint64_t> decode_collect_paths(const DecodeChunk& c, uint32_t K, const std::vector<uint32_t>& np,

@@ -101,6 +101,10 @@ struct Options {
   bool have_sample = false;  // (carmel_hip_decode_sample, seeded by -R); not carmel's -G, which generates from the whole machine
   std::string posterior_counts;  // --posterior-counts=FILE: the composed machine with every arc's expected count over all derivations
   bool have_posterior = false;   // of the lines as its weight (carmel_hip_decode_posterior), written to FILE
+  std::string pair_lines;  // --pair-lines=FILE (carmel's --post-b=FILE): line k of FILE is the other side's line of line k; every pair's
+  bool have_pair_lines = false;  // best derivation is printed in place of the line's (carmel_hip_decode_pairs)
+  std::string pair_alignments;   // --pair-alignments=OUT: every pair's best path as in:out symbol pairs, one line a pair
+  bool have_pair_alignments = false;
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };

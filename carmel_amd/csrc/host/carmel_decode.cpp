@@ -14,6 +14,14 @@
 // replaced by its expected number of uses over all derivations of the lines, every line weighing 1 (carmel_hip_decode_posterior,
 // csrc/decode_posterior.hip: the E-step of carmel -t for these lines); every arc is written, one never used with weight 0.
 // Nothing on stdout or stderr changes.
+// --pair-lines=FILE (carmel's --post-b=FILE, carmel.cc:569-597): line k of FILE is the OTHER side's line of line k, and what is
+// decoded is the pair -- its best derivation (carmel_hip_decode_pairs, csrc/decode_pairs.hip) in place of the line's, and with
+// --sum-paths the sum of the pair's derivations (carmel_hip_decode_pairs_sum) in the "Sum (all paths)" line, the one-sided sums
+// staying in the block before it.  Every pair prints exactly one line, its best path or the fill line: the reference prints
+// nothing for a line that has a derivation alone but none as a pair (carmel.cc:588-591, 1367), which would leave stdout without a
+// line-to-pair correspondence; this is a deliberate deviation.  --pair-alignments=OUT writes every pair's best path as
+// space-separated in:out symbol names (*e* for epsilon), an empty line for a pair without a derivation: the -I / -O / -@ forms
+// of a pair's path only spell the two lines again.
 #include <cctype>
 #include "carmel_cli.hpp"
 using namespace carmel_host;
@@ -28,6 +36,9 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   std::vector<uint64_t> off = std::vector<uint64_t>(1, 0);
   std::vector<uint32_t> sym;
   double n_symbols = 0;  // carmel.cc:1277-1283: the sum of the lines' lengths
+  // --pair-lines: the other side's line of every line, in the same form
+  std::vector<uint64_t> off2 = std::vector<uint64_t>(1, 0);
+  std::vector<uint32_t> sym2;
   // line l's paths are line_paths[l] .. line_paths[l + 1]; path p has the search's cost best[p] and the arcs
   // path[path_off[p] .. path_off[p + 1])
   std::vector<double> best;
@@ -37,9 +48,12 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   size_t n_0prob = 0;
   double n_prob = 0, prod_viterbi = 0;
   // --sum-paths (post_compose, carmel.cc:555-599): the lines whose sum of all paths is not zero, and the product of those sums
-  double pre_n_prob = 0, prod_sum = 0;
+  // (with --pair-lines the block before the report keeps the one-sided sums, prod_pre; prod_sum multiplies the pairs' sums)
+  double pre_n_prob = 0, prod_sum = 0, prod_pre = 0;
 
   int read_lines(const std::string& text, bool side_out);
+  int read_pair_lines(const std::string& text, bool side_out);
+  void pair_alignments() const;
   void decode(carmel_hip_decoder* d, size_t kbest);
   void sum_paths(carmel_hip_decoder* d);
   void posterior_counts(carmel_hip_decoder* d) const;
@@ -75,6 +89,33 @@ int Batch::read_lines(const std::string& text, bool side_out) {
   return 0;
 }
 
+// --pair-lines: line k of the file, in the alphabet of the side the lines are not on (carmel.cc:569-582)
+int Batch::read_pair_lines(const std::string& text, bool side_out) {
+  size_t p = 0;
+  for (size_t l = 0; l < lines.size(); ++l) {  // (lines beyond the last line are ignored)
+    if (p >= text.size()) {
+      std::cerr << "--pair-lines file didn't have as many lines as -b file.\n";
+      return -3;
+    }
+    size_t e = text.find('\n', p);
+    if (e == std::string::npos) e = text.size();
+    std::string ln = text.substr(p, e - p);
+    p = e + 1;
+    if (!ln.empty() && ln.back() == '\r') ln.pop_back();
+    std::vector<uint32_t> ids;
+    M.symbols_of_line(ln, !side_out, ids);
+    const SymbolTable& tab = side_out ? M.in_syms : M.out_syms;
+    for (uint32_t id : ids)
+      if (std::isdigit((unsigned char)tab.names[id][0])) {
+        std::cerr << "For --pair-lines=" << o.pair_lines << ", couldn't handle input line: " << ln << "\n";
+        return -3;
+      }
+    sym2.insert(sym2.end(), ids.begin(), ids.end());
+    off2.push_back(sym2.size());
+  }
+  return 0;
+}
+
 void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   const size_t n = lines.size();
   line_paths.assign(n + 1, 0);
@@ -94,7 +135,11 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   } else {
     std::vector<double> best1(n);
     std::vector<uint64_t> off1(n + 1);
-    hip_check(carmel_hip_decode(d, n, off.data(), sym.data(), best1.data(), off1.data()), "carmel_hip_decode");
+    if (o.have_pair_lines)
+      hip_check(carmel_hip_decode_pairs(d, n, off.data(), sym.data(), off2.data(), sym2.data(), best1.data(), off1.data()),
+                "carmel_hip_decode_pairs");
+    else
+      hip_check(carmel_hip_decode(d, n, off.data(), sym.data(), best1.data(), off1.data()), "carmel_hip_decode");
     path.resize(std::max<uint64_t>(off1[n], 1));
     hip_check(carmel_hip_decoder_get_paths(d, path.data()), "carmel_hip_decoder_get_paths");
     path_off.assign(1, 0);
@@ -110,7 +155,7 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   if (timing_on()) {
     double kms = 0;
     carmel_hip_decoder_last_ms(d, &kms);
-    std::cerr << (o.have_sample ? "timing: sample " : "timing: decode ")
+    std::cerr << (o.have_sample ? "timing: sample " : o.have_pair_lines ? "timing: pairs " : "timing: decode ")
               << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
               << " s (kernels " << kms * 1e-3 << " s)\n";
   }
@@ -121,7 +166,12 @@ void Batch::sum_paths(carmel_hip_decoder* d) {
   const size_t n = lines.size();
   std::vector<double> sums(n);
   const auto t0 = std::chrono::steady_clock::now();
-  hip_check(carmel_hip_decode_sum(d, n, off.data(), sym.data(), sums.data()), "carmel_hip_decode_sum");
+  const int rc = carmel_hip_decode_sum(d, n, off.data(), sym.data(), sums.data());
+  if (o.have_pair_lines && rc == CARMEL_HIP_ERR_UNSUPPORTED) {  // an insertion loop *e*:y: an epsilon cycle for a line, none for a pair
+    std::cerr << "The epsilon arcs of the lines' side have a cycle: no sum of all paths of the lines alone, before --pair-lines.\n";
+    sums.assign(n, kNegInf);
+  } else
+    hip_check(rc, "carmel_hip_decode_sum");
   if (timing_on()) {
     double kms = 0;
     carmel_hip_decoder_last_ms(d, &kms);
@@ -131,8 +181,41 @@ void Batch::sum_paths(carmel_hip_decoder* d) {
   for (size_t l = 0; l < n; ++l)
     if (sums[l] > kNegInf) {
       ++pre_n_prob;
-      prod_sum += sums[l];
+      prod_pre += sums[l];
     }
+  if (!o.have_pair_lines) {
+    prod_sum = prod_pre;
+    return;
+  }
+  const auto t1 = std::chrono::steady_clock::now();
+  hip_check(carmel_hip_decode_pairs_sum(d, n, off.data(), sym.data(), off2.data(), sym2.data(), sums.data()),
+            "carmel_hip_decode_pairs_sum");
+  if (timing_on()) {
+    double kms = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    std::cerr << "timing: pairs sum " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count()
+              << " s (kernels " << kms * 1e-3 << " s)\n";
+  }
+  for (size_t l = 0; l < n; ++l)  // carmel.cc:594-599: prod_sum *= the sum of the pair's composition
+    if (sums[l] > kNegInf) prod_sum += sums[l];
+}
+
+// every pair's best path as in:out symbol names, one line a pair
+void Batch::pair_alignments() const {
+  std::string buf;
+  for (size_t l = 0; l < lines.size(); ++l) {
+    for (uint64_t p = line_paths[l]; p < line_paths[l + 1]; ++p)
+      for (uint64_t k = path_off[p]; k < path_off[p + 1]; ++k) {
+        const HArc& a = *arc_of[path[k]];
+        if (k > path_off[p]) buf += ' ';
+        buf += (a.in ? M.in_syms.names[a.in] : std::string("*e*")) + ":" + (a.out ? M.out_syms.names[a.out] : std::string("*e*"));
+      }
+    buf += '\n';
+  }
+  std::ofstream of(o.pair_alignments.c_str());
+  of << buf;
+  of.close();
+  if (!of) throw std::runtime_error("--pair-alignments: cannot write " + o.pair_alignments);
 }
 
 // every arc's expected count over the derivations of all lines, as the weights of a copy of the machine, into the file
@@ -237,7 +320,7 @@ void Batch::report() const {
   const size_t n = lines.size();
   if (o.sum && pre_n_prob) {  // the lines post_compose saw: those with a derivation (the name passed is " inputs", carmel.cc:361)
     std::cerr << "Derivations found for all " << pre_n_prob << "  inputs.\n";
-    log_ppx(pre_n_prob, prod_sum, 0);
+    log_ppx(pre_n_prob, prod_pre, 0);
   }
   if (n_0prob)
     std::cerr << "No derivations found for " << n_0prob << " of " << n << " inputs.\n";
@@ -262,6 +345,8 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
     std::cerr << "No lines of input provided.\n";
     return 0;
   }
+  if (o.have_pair_lines)
+    if (int rc = b.read_pair_lines(slurp(o.pair_lines.c_str()), side_out)) return rc;
   std::vector<uint32_t> src, dst, in, out, group;
   std::vector<double> logw;
   M.flatten(src, dst, in, out, logw, group);
@@ -278,6 +363,7 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
   if (o.sum) b.sum_paths(d);
   if (o.have_posterior) b.posterior_counts(d);
   b.print_paths(kbest, quiet);
+  if (o.have_pair_alignments) b.pair_alignments();
   b.report();
   return 0;
 }

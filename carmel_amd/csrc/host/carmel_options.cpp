@@ -122,6 +122,14 @@ Options parse_args(int argc, char** argv) {
         o.posterior_counts = v;
         o.have_posterior = true;
       }
+      else if (k == "pair-lines") {  // carmel's --post-b=FILE under another name (carmel.cc:569-597): --post-b itself stays refused
+        o.pair_lines = v;
+        o.have_pair_lines = true;
+      }
+      else if (k == "pair-alignments") {  // not a carmel option: every pair's best path as in:out symbol pairs
+        o.pair_alignments = v;
+        o.have_pair_alignments = true;
+      }
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")

@@ -8,6 +8,8 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     sums = d.sum(lines)                # ln of every line's sum over ALL its derivations (carmel -b --sum; csrc/decode_sum.hip)
     weights, spaths = d.sample(lines, n, seed=0)   # n derivations per line, each drawn with probability weight / sum
     sums, counts = d.posterior(lines, weights=None)   # expected uses of every arc over all derivations of the lines
+    best, paths = d.decode_pairs(lines, lines2)    # lines2: the other side's line of every pair (carmel --post-b=FILE)
+    sums = d.sum_pairs(lines, lines2)              # ln of every pair's sum over all its derivations (csrc/decode_pairs.hip)
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -16,7 +18,9 @@ their arc ids; rank 0 is decode's path.  sample returns the same shapes: a line 
 order, duplicates kept; sample s of line l depends on the machine, the line, the seed, l and s alone.  posterior returns sum's
 sums, bit for bit, and counts[a] = the sum over the lines with a derivation of weights[l] (1 without weights) times the expected
 number of uses of arc a over line l's derivations, each derivation weighing weight / sum (csrc/decode_posterior.hip: forward and
-backward trellis); the sums are fixed to the bit, the counts up to the order of the device's atomic adds."""
+backward trellis); the sums are fixed to the bit, the counts up to the order of the device's atomic adds.
+A pair (lines[l], lines2[l]) is a line of the decoder's side and a line of the other side, in that side's alphabet; its
+derivations spell both.  decode_pairs returns decode's shapes (the Viterbi alignment of every pair), sum_pairs sum's."""
 import ctypes as C
 
 import numpy as np
@@ -103,6 +107,29 @@ class Decoder(object):
         off, sym = _pack(lines)
         out = np.empty(len(lines))
         check(lib.carmel_hip_decode_sum(self._h, len(lines), ptr(off), ptr(sym), ptr(out)), "carmel_hip_decode_sum")
+        return out
+
+    def decode_pairs(self, lines, lines2):
+        """-> (best, paths) as decode returns them, over the derivations that spell lines[l] on this side and lines2[l] on the other"""
+        assert len(lines) == len(lines2)
+        off, sym = _pack(lines)
+        off2, sym2 = _pack(lines2)
+        best = np.empty(len(lines))
+        path_off = np.zeros(len(lines) + 1, np.uint64)
+        check(lib.carmel_hip_decode_pairs(self._h, len(lines), ptr(off), ptr(sym), ptr(off2), ptr(sym2), ptr(best), ptr(path_off)),
+              "carmel_hip_decode_pairs")
+        arcs = np.zeros(max(int(path_off[-1]), 1), np.uint32)
+        check(lib.carmel_hip_decoder_get_paths(self._h, ptr(arcs)), "carmel_hip_decoder_get_paths")
+        return best, [arcs[int(path_off[l]):int(path_off[l + 1])].copy() for l in range(len(lines))]
+
+    def sum_pairs(self, lines, lines2):
+        """-> f64 array: per pair, the ln of the sum over all its derivations of their weights (-inf: no derivation)"""
+        assert len(lines) == len(lines2)
+        off, sym = _pack(lines)
+        off2, sym2 = _pack(lines2)
+        out = np.empty(len(lines))
+        check(lib.carmel_hip_decode_pairs_sum(self._h, len(lines), ptr(off), ptr(sym), ptr(off2), ptr(sym2), ptr(out)),
+              "carmel_hip_decode_pairs_sum")
         return out
 
     def posterior(self, lines, weights=None):

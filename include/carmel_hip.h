@@ -618,6 +618,31 @@ int carmel_hip_decode_posterior(carmel_hip_decoder* d, uint64_t n_lines, const u
                                 const double* line_weight /* nullable */, double* sum_logw /* [n_lines], nullable */,
                                 double* arc_count /* [n_arcs], overwritten */);
 
+/* ---- batch pair decoding (carmel --post-b=FILE; csrc/decode_pairs.hip) ----
+ * Replaces: post_compose's second composition with the parallel line and the best path / sum of the result (carmel.cc:569-597,
+ * the switch at 1781-1784).  A pair is (x, y): x a line of the decoder's matched side (off / sym, the CSR every decode entry
+ * point takes), y a line of the OTHER side in that side's alphabet (off2 / sym2, the same CSR form, n_pairs lines each).  A
+ * derivation of the pair is a path from state 0 to the final state that uses no arc of weight zero, whose matched-side symbols
+ * (epsilon dropped) spell x and whose other-side symbols spell y; a symbol no arc carries, on either side, means none.
+ * best_logw[l] is the ln weight of pair l's best derivation, its arcs' logs added from the END as carmel_hip_decode reports them
+ * (-inf and an empty path: no derivation); path_off (n_pairs + 1 entries) delimits the paths carmel_hip_decoder_get_paths
+ * returns.  The trellis runs over (position in x, position in y, state), anti-diagonal by anti-diagonal; only a STRICTLY better
+ * candidate replaces a node's value, the candidates taken as matched arcs in arc-id order, then matched-side-epsilon arcs in
+ * arc-id order: results do not depend on chunking, memory tier or launch order.  Only the arcs with epsilon on BOTH
+ * sides need an order inside a cell: an insertion loop *e*:y, which carmel_hip_decode_sum must refuse as an epsilon cycle, is
+ * legal here.  A cycle of arcs with epsilon on both sides (weight > 0) fails with CARMEL_HIP_ERR_UNSUPPORTED, naming the cycle,
+ * nothing is written and the handle stays usable.  A null d, off, off2, best_logw or path_off, bad offsets on either side, or
+ * n_pairs >= 2^32: CARMEL_HIP_ERR_ARG.  May alternate with the other decode entry points on one handle, and sees the weights of
+ * carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers the kernels. */
+int carmel_hip_decode_pairs(carmel_hip_decoder* d, uint64_t n_pairs, const uint64_t* off, const uint32_t* sym, const uint64_t* off2,
+                            const uint32_t* sym2, double* best_logw, uint64_t* path_off);
+/* Replaces: post_compose's sum_acyclic_paths of the pair's composition (carmel.cc:594-599).  Pairs as for
+ * carmel_hip_decode_pairs.  sum_logw[l] = ln of the sum, over ALL derivations of pair l, of the product of their arcs' weights;
+ * -inf = no derivation.  The same trellis in the log semiring, every node's terms added in the one fixed order above and read
+ * out once, as carmel_hip_decode_sum does; no back-pointers are kept.  Errors as for carmel_hip_decode_pairs. */
+int carmel_hip_decode_pairs_sum(carmel_hip_decoder* d, uint64_t n_pairs, const uint64_t* off, const uint32_t* sym,
+                                const uint64_t* off2, const uint32_t* sym2, double* sum_logw);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;

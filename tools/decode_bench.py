@@ -13,10 +13,15 @@ time), and writes that run's figures to --sample-out (profiles/decode_sample_ben
 kernel and call time, lines per second, the ratios to the sum's, the one-sample and the 1-best kernels' time, the total of the
 matched arcs' counts against the positions of the lines with a derivation), and writes that run's figures to --posterior-out
 (profiles/decode_posterior_bench.json).
+--pairs pairs every line with the other-side string of its 1-best path (a line without a derivation with the empty string) and
+adds the pairs through carmel_hip_decode_pairs and carmel_hip_decode_pairs_sum (csrc/decode_pairs.hip), beside the 1-best decode
+and the sum of the same run ("pairs": kernel and call time of both, pairs per second, trellis nodes per second, the ratios to the
+1-best and the sum kernels' time, whether every pair of a line with a derivation has one), and writes that run's figures to
+--pairs-out (profiles/decode_pairs_bench.json).
 Prints one JSON object.
 
     python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...] [--sum]
-                                 [--sample 1 --sample 16] [--posterior]
+                                 [--sample 1 --sample 16] [--posterior] [--pairs]
 
 The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
 on the weights); the cluster and cipher commands use their committed trained members."""
@@ -57,6 +62,8 @@ def main():
     ap.add_argument("--sample-out", default=os.path.join(ROOT, "profiles", "decode_sample_bench.json"))
     ap.add_argument("--posterior", action="store_true")
     ap.add_argument("--posterior-out", default=os.path.join(ROOT, "profiles", "decode_posterior_bench.json"))
+    ap.add_argument("--pairs", action="store_true")
+    ap.add_argument("--pairs-out", default=os.path.join(ROOT, "profiles", "decode_pairs_bench.json"))
     a = ap.parse_args()
     sample_ns = a.sample + ([1] if a.posterior and 1 not in a.sample else [])  # (the posteriors are reported beside one sample a line)
     from carmel_amd.decode import Decoder
@@ -92,7 +99,7 @@ def main():
                          "rank0_equals_1best": bool(np.array_equal(logw[line_paths[:-1][np.diff(line_paths) > 0].astype(np.int64)],
                                                                    best[~np.isneginf(best)]))}
     sums = None
-    if a.sum or sample_ns:  # (the samples and the posteriors are reported beside the sum of the same run)
+    if a.sum or sample_ns or a.pairs:  # (the samples, the posteriors and the pairs are reported beside the sum of the same run)
         d.sum(lines[:1000])
         kms_s, wall_s = [], []
         for _ in range(a.reps):
@@ -135,6 +142,33 @@ def main():
                 "sums_equal_the_sum": bool(psums.tobytes() == total.tobytes()),
                 "matched_count": float(counts[w["osym"] != 0].sum()),
                 "positions_with_a_derivation": int(sum(len(x) for x, h in zip(lines, has) if h))}
+    pairs = None
+    if a.pairs:
+        isym = np.asarray(w["isym"])
+        other = [isym[p][isym[p] != 0] for p in paths]  # the tags of the line's best path
+        d.decode_pairs(lines[:1000], other[:1000])
+        d.sum_pairs(lines[:1000], other[:1000])
+        kms_b, wall_b, kms_t, wall_t = [], [], [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            pbest, ppaths = d.decode_pairs(lines, other)
+            wall_b.append((time.perf_counter() - t0) * 1e3)
+            kms_b.append(d.last_ms())
+            t0 = time.perf_counter()
+            psum = d.sum_pairs(lines, other)
+            wall_t.append((time.perf_counter() - t0) * 1e3)
+            kms_t.append(d.last_ms())
+        nodes = int(sum((len(x) + 1) * (len(y) + 1) for x, y in zip(lines, other))) * int(w["n_states"])
+        pairs = {"best": {"kernel_ms": float(np.median(kms_b)), "kernel_ms_all": kms_b, "call_ms": float(np.median(wall_b))},
+                 "sum": {"kernel_ms": float(np.median(kms_t)), "kernel_ms_all": kms_t, "call_ms": float(np.median(wall_t))},
+                 "trellis_nodes": nodes, "no_derivation": int(np.isneginf(pbest).sum()),
+                 "a_pair_has_a_derivation_where_its_line_has": bool(np.array_equal(np.isneginf(pbest), np.isneginf(best)) and
+                                                                    np.array_equal(np.isneginf(psum), np.isneginf(best))),
+                 # (the line's best path is a derivation of the pair: the pair's best is at least as good, to the bit)
+                 "pair_best_equals_1best": bool(np.array_equal(pbest, best))}
+        for v in (pairs["best"], pairs["sum"]):
+            v["pairs_per_s"] = len(lines) / (v["kernel_ms"] * 1e-3)
+            v["nodes_per_s"] = nodes / (v["kernel_ms"] * 1e-3)
     d.close()
     n_pos = int(sum(len(x) for x in lines))
     # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
@@ -186,6 +220,15 @@ def main():
             json.dump({"workload": res["workload"], "machine": res["machine"], "reps": a.reps,
                        "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
                                     "lines_per_s": res["lines_per_s"]}, "sum": sums, "sample_1": samples["1"], "posterior": post}, f)
+            f.write("\n")
+    if pairs:
+        pairs["best"]["kernel_ms_over_1best"] = pairs["best"]["kernel_ms"] / kms
+        pairs["sum"]["kernel_ms_over_sum"] = pairs["sum"]["kernel_ms"] / sums["kernel_ms"]
+        res["pairs"] = pairs
+        with open(a.pairs_out, "w") as f:
+            json.dump({"workload": res["workload"] + ", every line paired with the tags of its best path", "machine": res["machine"],
+                       "reps": a.reps, "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
+                                                    "lines_per_s": res["lines_per_s"]}, "sum": sums, "pairs": pairs}, f)
             f.write("\n")
     if a.sum:
         with open(a.sum_out, "w") as f:
