@@ -348,6 +348,36 @@ int carmel_hip_decoder::upload_tables() {
     for (size_t L = 0; L + 1 < h_plvl_ent.size(); ++L) h_plvl_ent[L + 1] += h_plvl_ent[L];
   }
   if (h_plvl_ent.empty()) h_plvl_ent.assign(1, 0);
+  // their outgoing view (DecodePairOutTables): the other side's symbols beside the outgoing matched CSR above, and the same
+  // epsilon arcs by (00 level of the source, source, arc id), one entry per source; nothing if the 00 arcs have a cycle
+  std::vector<uint32_t> h_omosym, poeps, h_polvl_ent(1, 0), h_poent_src, h_poent_arc, h_poedst, h_poeid, h_poeosym;
+  std::vector<double> h_poew;
+  std::vector<uint8_t> h_poepsout(Q, 0);
+  for (uint32_t k : omatched) h_omosym.push_back(osym[k]);
+  uint32_t max_oseg = 0;
+  for (uint32_t x = 0; x < n_syms; ++x) max_oseg = std::max(max_oseg, h_osym_seg[x + 1] - h_osym_seg[x]);
+  if (pair_cycle.empty() && !peps.empty()) {
+    poeps = peps;
+    std::sort(poeps.begin(), poeps.end(), [&](uint32_t a, uint32_t b) {
+      return plevel[src[a]] != plevel[src[b]] ? plevel[src[a]] < plevel[src[b]] : src[a] != src[b] ? src[a] < src[b] : a < b;
+    });
+    h_polvl_ent.assign(pair_levels + 2, 0);
+    for (size_t j = 0; j < poeps.size(); ++j) {
+      const uint32_t k = poeps[j];
+      if (j == 0 || src[k] != src[poeps[j - 1]]) {
+        h_poent_src.push_back(src[k]);
+        h_poent_arc.push_back((uint32_t)j);
+        h_polvl_ent[plevel[src[k]] + 1]++;
+      }
+      h_poedst.push_back(dst[k]);
+      h_poew.push_back(logw[k]);
+      h_poeid.push_back(k);
+      h_poeosym.push_back(osym[k]);
+      h_poepsout[src[k]] = 1;
+    }
+    for (size_t L = 0; L + 1 < h_polvl_ent.size(); ++L) h_polvl_ent[L + 1] += h_polvl_ent[L];
+  }
+  h_poent_arc.push_back((uint32_t)poeps.size());
   std::vector<uint8_t> h_aflags(n_arcs);
   for (uint64_t k = 0; k < n_arcs; ++k) h_aflags[k] = (msym[k] != 0 ? 1 : 0) | (osym[k] != 0 ? 2 : 0);
   hipStream_t s = stream;
@@ -360,6 +390,15 @@ int carmel_hip_decoder::upload_tables() {
   HIPCHK(p_e_id.upload(h_peid, s));
   HIPCHK(p_e_osym.upload(h_peosym, s));
   HIPCHK(a_flags.upload(h_aflags, s));
+  HIPCHK(po_m_osym.upload(h_omosym, s));
+  HIPCHK(po_lvl_ent.upload(h_polvl_ent, s));
+  HIPCHK(po_ent_src.upload(h_poent_src, s));
+  HIPCHK(po_ent_arc.upload(h_poent_arc, s));
+  HIPCHK(po_e_dst.upload(h_poedst, s));
+  HIPCHK(po_e_w.upload(h_poew, s));
+  HIPCHK(po_e_id.upload(h_poeid, s));
+  HIPCHK(po_e_osym.upload(h_poeosym, s));
+  HIPCHK(po_eps_out.upload(h_poepsout, s));
   HIPCHK(sym_seg.upload(h_sym_seg, s));
   HIPCHK(seg_dst.upload(h_seg_dst, s));
   HIPCHK(seg_arc.upload(h_seg_arc, s));
@@ -397,6 +436,9 @@ int carmel_hip_decoder::upload_tables() {
                        o_ent_src.p, o_ent_arc.p, o_e_dst.p,   o_e_w.p,   o_e_id.p, eps_out.p, o_st_ent.p};
   TP = DecodePairTables{p_m_osym.p, (uint32_t)h_plvl_ent.size() - 1, max_seg, p_lvl_ent.p, p_ent_dst.p, p_ent_arc.p, p_e_src.p,
                         p_e_w.p,    p_e_id.p, p_e_osym.p};
+  TPO = DecodePairOutTables{o_sym_seg.p,  o_seg_src.p,  o_seg_arc.p, o_m_dst.p, o_m_w.p,   o_m_id.p,    po_m_osym.p,
+                            (uint32_t)h_polvl_ent.size() - 1, max_oseg, po_lvl_ent.p, po_ent_src.p, po_ent_arc.p, po_e_dst.p,
+                            po_e_w.p, po_e_id.p, po_e_osym.p, po_eps_out.p};
   T = DecodeTables{Q, final_state, n_syms, sym_seg.p, seg_dst.p, seg_arc.p, m_src.p, m_w.p, m_id.p, n_levels, eps_cyclic ? 1 : 0,
                    lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size(), st_ent.p};
   return CARMEL_HIP_OK;

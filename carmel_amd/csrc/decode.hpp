@@ -1,5 +1,5 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
-// samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip) share: the prepared tables, the decoder
+// samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip and decode_pairs_posterior.hip) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built and
 // uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum share is
@@ -78,6 +78,31 @@ struct DecodePairTables {
   const uint32_t* e_osym;   // 0: a 00 arc (source in the same cell); else a 0M arc (source in cell (i, j - 1))
 };
 
+// The outgoing view of DecodePairTables, for the backward pass of the pair arc posteriors (decode_pairs_posterior.hip): an arc is
+// filed under its source.  The matched CSR is DecodeOutTables' (it has no levels in it) with the other side's symbols beside it;
+// the matched-side-epsilon arcs are filed by the 00 level of their SOURCE (DecodePairTables' levels: a 00 arc's destination is of
+// strictly higher level than its source, a 0M arc leaves the cell), never by DecodeOutTables' epsilon levels, which a 0M loop
+// takes away.  Empty epsilon lists when the 00 arcs have a cycle (the pair entry points refuse).
+struct DecodePairOutTables {
+  const uint32_t* sym_seg;  // [n_syms + 1] -> segments          (DecodeOutTables')
+  const uint32_t* seg_src;  // [n_seg]
+  const uint32_t* seg_arc;  // [n_seg + 1] -> matched arcs
+  const uint32_t* m_dst;    // matched arcs, by (symbol, src, arc id)
+  const double* m_w;
+  const uint32_t* m_id;
+  const uint32_t* m_osym;   // parallel to m_dst / m_w / m_id
+  uint32_t n_levels;        // 1 + the highest 00 level of a state that an epsilon arc leaves (0: no epsilon arcs)
+  uint32_t max_seg;         // the most source segments a matched symbol has
+  const uint32_t* lvl_ent;  // [n_levels + 1] -> entries (one source state each), by the 00 level of the state
+  const uint32_t* ent_src;
+  const uint32_t* ent_arc;  // [n_ent + 1] -> epsilon arcs
+  const uint32_t* e_dst;    // epsilon arcs, by (00 level of src, src, arc id)
+  const double* e_w;
+  const uint32_t* e_id;
+  const uint32_t* e_osym;   // 0: a 00 arc (destination in the same cell); else a 0M arc (destination in cell (i, j + 1))
+  const uint8_t* eps_out;   // [n_states]: a matched-side-epsilon arc (of weight > 0) leaves the state
+};
+
 // a chunk's lines, as every trellis kernel takes them: one workgroup of kLanes lanes per line
 struct DecodeLines {
   const uint64_t* off;    // chunk-local CSR of the lines' symbols
@@ -110,7 +135,7 @@ struct carmel_hip_decoder {
   DevBuf<uint8_t> a_eps;
   DevBuf<uint8_t> eps_in;  // [|Q|]: the state is the destination of an epsilon arc of non-zero weight (k-best: its epsilon level is >= 1)
   DecodeTables T;
-  // the outgoing view (DecodeOutTables), and the arc counts of a carmel_hip_decode_posterior call: zeroed once per call,
+  // the outgoing view (DecodeOutTables), and the arc counts of a carmel_hip_decode_posterior or carmel_hip_decode_pairs_posterior call: zeroed once per call,
   // accumulated over all its chunks
   DevBuf<uint32_t> o_sym_seg, o_seg_src, o_seg_arc, o_m_dst, o_m_id, o_lvl_ent, o_ent_src, o_ent_arc, o_e_dst, o_e_id, o_st_ent;
   DevBuf<double> o_m_w, o_e_w, count;
@@ -122,6 +147,11 @@ struct carmel_hip_decoder {
   DevBuf<double> p_e_w;
   DevBuf<uint8_t> a_flags;  // per arc, for the pair walk: bit 0 the matched symbol is not epsilon, bit 1 the other symbol is not
   DecodePairTables TP;
+  // their outgoing view (DecodePairOutTables), for carmel_hip_decode_pairs_posterior
+  DevBuf<uint32_t> po_m_osym, po_lvl_ent, po_ent_src, po_ent_arc, po_e_dst, po_e_id, po_e_osym;
+  DevBuf<double> po_e_w;
+  DevBuf<uint8_t> po_eps_out;
+  DecodePairOutTables TPO;
   uint32_t pair_levels = 0;  // the highest 00 level
   std::string pair_cycle;
   std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)

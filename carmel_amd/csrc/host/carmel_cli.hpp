@@ -105,6 +105,8 @@ struct Options {
   bool have_pair_lines = false;  // best derivation is printed in place of the line's (carmel_hip_decode_pairs)
   std::string pair_alignments;   // --pair-alignments=OUT: every pair's best path as in:out symbol pairs, one line a pair
   bool have_pair_alignments = false;
+  std::string pair_counts;       // --pair-counts=FILE: the composed machine with every arc's expected count over all derivations
+  bool have_pair_counts = false;  // of the pairs as its weight (carmel_hip_decode_pairs_posterior), written to FILE
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };

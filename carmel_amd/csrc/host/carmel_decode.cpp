@@ -21,7 +21,9 @@
 // nothing for a line that has a derivation alone but none as a pair (carmel.cc:588-591, 1367), which would leave stdout without a
 // line-to-pair correspondence; this is a deliberate deviation.  --pair-alignments=OUT writes every pair's best path as
 // space-separated in:out symbol names (*e* for epsilon), an empty line for a pair without a derivation: the -I / -O / -@ forms
-// of a pair's path only spell the two lines again.
+// of a pair's path only spell the two lines again.  --pair-counts=FILE is --posterior-counts=FILE for the pairs: the composed
+// machine, every arc's weight replaced by its expected number of uses over all derivations of the pairs, every pair weighing 1
+// (carmel_hip_decode_pairs_posterior, csrc/decode_pairs_posterior.hip: the E-step of carmel -t for these pairs).
 #include <cctype>
 #include "carmel_cli.hpp"
 using namespace carmel_host;
@@ -57,6 +59,8 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   void decode(carmel_hip_decoder* d, size_t kbest);
   void sum_paths(carmel_hip_decoder* d);
   void posterior_counts(carmel_hip_decoder* d) const;
+  void pair_counts(carmel_hip_decoder* d) const;
+  void write_counts(std::vector<double>& count, const char* option, const std::string& file) const;
   void format_path(uint64_t p, std::string& buf) const;
   void print_paths(size_t kbest, bool quiet);
   void log_ppx(double n_pairs, double prod, size_t n_0) const;
@@ -230,13 +234,34 @@ void Batch::posterior_counts(carmel_hip_decoder* d) const {
     std::cerr << "timing: posterior " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
               << " s (kernels " << kms * 1e-3 << " s)\n";
   }
+  write_counts(count, "--posterior-counts", o.posterior_counts);
+}
+
+// the same over the derivations of all pairs
+void Batch::pair_counts(carmel_hip_decoder* d) const {
+  std::vector<double> count(std::max<size_t>(M.num_arcs(), 1));
+  const auto t0 = std::chrono::steady_clock::now();
+  hip_check(carmel_hip_decode_pairs_posterior(d, lines.size(), off.data(), sym.data(), off2.data(), sym2.data(), nullptr, nullptr,
+                                              count.data()),
+            "carmel_hip_decode_pairs_posterior");
+  if (timing_on()) {
+    double kms = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    std::cerr << "timing: pairs posterior " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+              << " s (kernels " << kms * 1e-3 << " s)\n";
+  }
+  write_counts(count, "--pair-counts", o.pair_counts);
+}
+
+// a copy of the machine with the counts as its weights, every arc written, into the file
+void Batch::write_counts(std::vector<double>& count, const char* option, const std::string& file) const {
   for (double& c : count) c = c > 0 ? std::log(c) : kNegInf;
   Transducer counted(M);
   counted.set_weights(count.data());
-  std::ofstream of(o.posterior_counts.c_str());
+  std::ofstream of(file.c_str());
   of << counted.to_text(o.flags[(unsigned)'J'], o.flags[(unsigned)'H'], ws, /*include_zero=*/true);
   of.close();
-  if (!of) throw std::runtime_error("--posterior-counts: cannot write " + o.posterior_counts);
+  if (!of) throw std::runtime_error(std::string(option) + ": cannot write " + file);
 }
 
 // one path of a line into buf, as path_print writes it
@@ -362,6 +387,7 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
   b.decode(d, kbest);
   if (o.sum) b.sum_paths(d);
   if (o.have_posterior) b.posterior_counts(d);
+  if (o.have_pair_counts) b.pair_counts(d);
   b.print_paths(kbest, quiet);
   if (o.have_pair_alignments) b.pair_alignments();
   b.report();

@@ -34,7 +34,8 @@ static int print_help() {
                "over all derivations of the lines as its weight (no epsilon cycles); "
                "pair decoding: --pair-lines=FILE with -b / -i and -k 1 (carmel's --post-b=FILE: line k of FILE is the other side of line k) "
                "prints every pair's best derivation, --sum-paths then multiplies the pairs' sums, --pair-alignments=OUT writes "
-               "the best paths as in:out symbol pairs (no cycles of *e*:*e* arcs); "
+               "the best paths as in:out symbol pairs, --pair-counts=FILE writes the composed machine with every arc's expected "
+               "count over all derivations of the pairs as its weight (no cycles of *e*:*e* arcs); "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -48,6 +49,11 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
       throw UsageError("--posterior-counts=FILE applies to batch decoding (-b or -i)");
     if (with_pairs) throw UsageError("--posterior-counts=FILE with -t / --train-cascade / -S is not implemented");
   }
+  if (o.have_pair_counts) {
+    if (o.pair_counts.empty()) throw UsageError("--pair-counts=FILE needs a file name");
+    if (with_pairs || o.train_cascade) throw UsageError("--pair-counts=FILE with -t / --train-cascade / -S is not implemented");
+    if (!o.have_pair_lines) throw UsageError("--pair-counts=FILE needs --pair-lines=FILE");
+  }
   if (o.have_pair_alignments && !o.have_pair_lines) throw UsageError("--pair-alignments=OUT needs --pair-lines=FILE");
   if (o.have_pair_lines) {
     if (o.pair_lines.empty()) throw UsageError("--pair-lines=FILE needs a file name");
@@ -55,7 +61,8 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
     if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i']) throw UsageError("--pair-lines=FILE applies to batch decoding (-b or -i with -k 1)");
     if (with_pairs) throw UsageError("--pair-lines=FILE with -t / --train-cascade / -S is not implemented");
     if (o.have_kbest || o.have_sample || o.have_posterior)
-      throw UsageError("--pair-lines=FILE with --kbest=N, --sample-paths=N or --posterior-counts=FILE is not implemented");
+      throw UsageError("--pair-lines=FILE with --kbest=N, --sample-paths=N or --posterior-counts=FILE is not implemented (the pairs' "
+                       "arc posteriors: --pair-counts=FILE)");
   }
   if (decoding) {
     if (o.have_sample) {

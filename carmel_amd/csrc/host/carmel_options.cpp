@@ -130,6 +130,10 @@ Options parse_args(int argc, char** argv) {
         o.pair_alignments = v;
         o.have_pair_alignments = true;
       }
+      else if (k == "pair-counts") {  // not a carmel option: every arc's expected count over the pairs (carmel_hip_decode_pairs_posterior)
+        o.pair_counts = v;
+        o.have_pair_counts = true;
+      }
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")

@@ -10,6 +10,7 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     sums, counts = d.posterior(lines, weights=None)   # expected uses of every arc over all derivations of the lines
     best, paths = d.decode_pairs(lines, lines2)    # lines2: the other side's line of every pair (carmel --post-b=FILE)
     sums = d.sum_pairs(lines, lines2)              # ln of every pair's sum over all its derivations (csrc/decode_pairs.hip)
+    sums, counts = d.posterior_pairs(lines, lines2, weights=None)   # expected uses of every arc over the pairs' derivations
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -20,7 +21,9 @@ sums, bit for bit, and counts[a] = the sum over the lines with a derivation of w
 number of uses of arc a over line l's derivations, each derivation weighing weight / sum (csrc/decode_posterior.hip: forward and
 backward trellis); the sums are fixed to the bit, the counts up to the order of the device's atomic adds.
 A pair (lines[l], lines2[l]) is a line of the decoder's side and a line of the other side, in that side's alphabet; its
-derivations spell both.  decode_pairs returns decode's shapes (the Viterbi alignment of every pair), sum_pairs sum's."""
+derivations spell both.  decode_pairs returns decode's shapes (the Viterbi alignment of every pair), sum_pairs sum's, and
+posterior_pairs posterior's: sum_pairs' sums, bit for bit, and the arcs' expected uses over the pairs' derivations
+(csrc/decode_pairs_posterior.hip: the pair trellis forwards and backwards)."""
 import ctypes as C
 
 import numpy as np
@@ -131,6 +134,20 @@ class Decoder(object):
         check(lib.carmel_hip_decode_pairs_sum(self._h, len(lines), ptr(off), ptr(sym), ptr(off2), ptr(sym2), ptr(out)),
               "carmel_hip_decode_pairs_sum")
         return out
+
+    def posterior_pairs(self, lines, lines2, weights=None):
+        """-> (sums, counts): sum_pairs(lines, lines2), and per arc its expected number of uses over the derivations of the pairs
+        (pair l counts weights[l] times, 1 without weights; weights are finite and >= 0); a pair without a derivation adds nothing"""
+        assert len(lines) == len(lines2)
+        off, sym = _pack(lines)
+        off2, sym2 = _pack(lines2)
+        sums = np.empty(len(lines))
+        counts = np.zeros(max(self.n_arcs, 1))
+        wt = None if weights is None else f64(weights)
+        assert wt is None or len(wt) == len(lines)
+        check(lib.carmel_hip_decode_pairs_posterior(self._h, len(lines), ptr(off), ptr(sym), ptr(off2), ptr(sym2), ptr(wt), ptr(sums),
+                                                    ptr(counts)), "carmel_hip_decode_pairs_posterior")
+        return sums, counts[:self.n_arcs]
 
     def posterior(self, lines, weights=None):
         """-> (sums, counts): sum(lines), and per arc its expected number of uses over the derivations of the lines (line l counts

@@ -642,6 +642,26 @@ int carmel_hip_decode_pairs(carmel_hip_decoder* d, uint64_t n_pairs, const uint6
  * out once, as carmel_hip_decode_sum does; no back-pointers are kept.  Errors as for carmel_hip_decode_pairs. */
 int carmel_hip_decode_pairs_sum(carmel_hip_decoder* d, uint64_t n_pairs, const uint64_t* off, const uint32_t* sym,
                                 const uint64_t* off2, const uint32_t* sym2, double* sum_logw);
+/* ---- batch pair arc posteriors (csrc/decode_pairs_posterior.hip) ----
+ * Stands in for: the forward/backward of carmel -t (train.cc:254-266, 698-860: the E-step's expected arc counts) over a corpus
+ * of (input, output) pairs, where the reference builds a derivation lattice per pair; here the pair trellis of
+ * carmel_hip_decode_pairs is walked forwards and backwards against a machine that is composed once.  Pairs and derivations as
+ * carmel_hip_decode_pairs defines them; weights, outputs and errors as carmel_hip_decode_posterior defines them: arc_count[a]
+ * (n_arcs entries, overwritten) is the sum over the pairs l that have a derivation of pair_weight[l] (1 if pair_weight is null)
+ * times the expected number of uses of arc a over the derivations of l, each weighted by w(d) / (the sum over all derivations
+ * of l); a pair without a derivation, or of weight 0, adds nothing.  sum_logw (n_pairs entries, may be null) gets every pair's
+ * sum of all derivations, bit for bit carmel_hip_decode_pairs_sum's, whatever the pair's weight.  The forward pass is that
+ * sum's with every node kept; the backward pass runs over the anti-diagonals from the last to the first, feeds every node's
+ * accumulator in one fixed order and adds every trellis edge's posterior exp((forward value of the source + arc weight) +
+ * backward value of the destination - the pair's sum) to its arc with an atomic add (DESIGN.md has the rule in full): sum_logw
+ * is fixed to the bit, arc_count up to the order of those adds.  A pair weight that is negative or not finite, a null d, off,
+ * off2 or arc_count, bad offsets on either side, or n_pairs >= 2^32: CARMEL_HIP_ERR_ARG, nothing is written.  An insertion loop
+ * *e*:y is legal; a cycle of arcs with epsilon on both sides fails with CARMEL_HIP_ERR_UNSUPPORTED, naming the cycle, nothing
+ * is written and the handle stays usable.  May alternate with the other decode entry points on one handle, and sees the weights
+ * of carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers both kernels. */
+int carmel_hip_decode_pairs_posterior(carmel_hip_decoder* d, uint64_t n_pairs, const uint64_t* off, const uint32_t* sym,
+                                      const uint64_t* off2, const uint32_t* sym2, const double* pair_weight /* nullable */,
+                                      double* sum_logw /* [n_pairs], nullable */, double* arc_count /* [n_arcs], overwritten */);
 
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */

@@ -18,10 +18,15 @@ adds the pairs through carmel_hip_decode_pairs and carmel_hip_decode_pairs_sum (
 and the sum of the same run ("pairs": kernel and call time of both, pairs per second, trellis nodes per second, the ratios to the
 1-best and the sum kernels' time, whether every pair of a line with a derivation has one), and writes that run's figures to
 --pairs-out (profiles/decode_pairs_bench.json).
+--pairs-posterior adds the same pairs through carmel_hip_decode_pairs_posterior (csrc/decode_pairs_posterior.hip), beside
+carmel_hip_decode_pairs_sum timed in the same loop ("pairs_posterior": kernel and call time of both, pairs per second, the kernels'
+time as a multiple of the pair sum's, whether the sums are the pair sum's bit for bit, the matched and the other-side arcs' counts
+against the lengths of the pairs with a derivation), and writes that run's figures to --pairs-posterior-out
+(profiles/decode_pairs_posterior_bench.json).
 Prints one JSON object.
 
     python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...] [--sum]
-                                 [--sample 1 --sample 16] [--posterior] [--pairs]
+                                 [--sample 1 --sample 16] [--posterior] [--pairs] [--pairs-posterior]
 
 The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
 on the weights); the cluster and cipher commands use their committed trained members."""
@@ -64,6 +69,8 @@ def main():
     ap.add_argument("--posterior-out", default=os.path.join(ROOT, "profiles", "decode_posterior_bench.json"))
     ap.add_argument("--pairs", action="store_true")
     ap.add_argument("--pairs-out", default=os.path.join(ROOT, "profiles", "decode_pairs_bench.json"))
+    ap.add_argument("--pairs-posterior", action="store_true")
+    ap.add_argument("--pairs-posterior-out", default=os.path.join(ROOT, "profiles", "decode_pairs_posterior_bench.json"))
     a = ap.parse_args()
     sample_ns = a.sample + ([1] if a.posterior and 1 not in a.sample else [])  # (the posteriors are reported beside one sample a line)
     from carmel_amd.decode import Decoder
@@ -169,6 +176,34 @@ def main():
         for v in (pairs["best"], pairs["sum"]):
             v["pairs_per_s"] = len(lines) / (v["kernel_ms"] * 1e-3)
             v["nodes_per_s"] = nodes / (v["kernel_ms"] * 1e-3)
+    ppost = None
+    if a.pairs_posterior:
+        isym = np.asarray(w["isym"])
+        other = [isym[p][isym[p] != 0] for p in paths]  # the tags of the line's best path
+        d.sum_pairs(lines[:1000], other[:1000])
+        d.posterior_pairs(lines[:1000], other[:1000])
+        kms_t, wall_t, kms_p, wall_p = [], [], [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            psum = d.sum_pairs(lines, other)
+            wall_t.append((time.perf_counter() - t0) * 1e3)
+            kms_t.append(d.last_ms())
+            t0 = time.perf_counter()
+            qsum, counts = d.posterior_pairs(lines, other)
+            wall_p.append((time.perf_counter() - t0) * 1e3)
+            kms_p.append(d.last_ms())
+        has = ~np.isneginf(qsum)
+        ppost = {"sum": {"kernel_ms": float(np.median(kms_t)), "kernel_ms_all": kms_t, "call_ms": float(np.median(wall_t))},
+                 "posterior": {"kernel_ms": float(np.median(kms_p)), "kernel_ms_all": kms_p, "call_ms": float(np.median(wall_p))},
+                 "trellis_nodes": int(sum((len(x) + 1) * (len(y) + 1) for x, y in zip(lines, other))) * int(w["n_states"]),
+                 "no_derivation": int((~has).sum()), "sums_equal_the_pair_sum": bool(qsum.tobytes() == psum.tobytes()),
+                 "matched_count": float(counts[w["osym"] != 0].sum()),
+                 "matched_positions_with_a_derivation": int(sum(len(x) for x, h in zip(lines, has) if h)),
+                 "other_count": float(counts[w["isym"] != 0].sum()),
+                 "other_positions_with_a_derivation": int(sum(len(y) for y, h in zip(other, has) if h))}
+        for v in (ppost["sum"], ppost["posterior"]):
+            v["pairs_per_s"] = len(lines) / (v["kernel_ms"] * 1e-3)
+        ppost["posterior"]["kernel_ms_over_pair_sum"] = ppost["posterior"]["kernel_ms"] / ppost["sum"]["kernel_ms"]
     d.close()
     n_pos = int(sum(len(x) for x in lines))
     # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
@@ -229,6 +264,12 @@ def main():
             json.dump({"workload": res["workload"] + ", every line paired with the tags of its best path", "machine": res["machine"],
                        "reps": a.reps, "one_best": {"kernel_ms": kms, "kernel_ms_all": ms, "call_ms": res["call_ms"],
                                                     "lines_per_s": res["lines_per_s"]}, "sum": sums, "pairs": pairs}, f)
+            f.write("\n")
+    if ppost:
+        res["pairs_posterior"] = ppost
+        with open(a.pairs_posterior_out, "w") as f:
+            json.dump({"workload": res["workload"] + ", every line paired with the tags of its best path", "machine": res["machine"],
+                       "reps": a.reps, "pairs_posterior": ppost}, f)
             f.write("\n")
     if a.sum:
         with open(a.sum_out, "w") as f:
