@@ -348,6 +348,8 @@ int carmel_hip_decoder::upload_tables() {
     for (size_t L = 0; L + 1 < h_plvl_ent.size(); ++L) h_plvl_ent[L + 1] += h_plvl_ent[L];
   }
   if (h_plvl_ent.empty()) h_plvl_ent.assign(1, 0);
+  std::vector<uint32_t> h_pstent(Q, kNone);  // the pair sampler's walk finds a state's matched-side-epsilon arcs through its entry
+  for (size_t e = 0; e < h_pent_dst.size(); ++e) h_pstent[h_pent_dst[e]] = (uint32_t)e;
   // their outgoing view (DecodePairOutTables): the other side's symbols beside the outgoing matched CSR above, and the same
   // epsilon arcs by (00 level of the source, source, arc id), one entry per source; nothing if the 00 arcs have a cycle
   std::vector<uint32_t> h_omosym, poeps, h_polvl_ent(1, 0), h_poent_src, h_poent_arc, h_poedst, h_poeid, h_poeosym;
@@ -389,6 +391,7 @@ int carmel_hip_decoder::upload_tables() {
   HIPCHK(p_e_w.upload(h_pew, s));
   HIPCHK(p_e_id.upload(h_peid, s));
   HIPCHK(p_e_osym.upload(h_peosym, s));
+  HIPCHK(p_st_ent.upload(h_pstent, s));
   HIPCHK(a_flags.upload(h_aflags, s));
   HIPCHK(po_m_osym.upload(h_omosym, s));
   HIPCHK(po_lvl_ent.upload(h_polvl_ent, s));
@@ -435,7 +438,7 @@ int carmel_hip_decoder::upload_tables() {
   TO = DecodeOutTables{o_sym_seg.p, o_seg_src.p, o_seg_arc.p, o_m_dst.p, o_m_w.p,  o_m_id.p,  o_lvl_ent.p,
                        o_ent_src.p, o_ent_arc.p, o_e_dst.p,   o_e_w.p,   o_e_id.p, eps_out.p, o_st_ent.p};
   TP = DecodePairTables{p_m_osym.p, (uint32_t)h_plvl_ent.size() - 1, max_seg, p_lvl_ent.p, p_ent_dst.p, p_ent_arc.p, p_e_src.p,
-                        p_e_w.p,    p_e_id.p, p_e_osym.p};
+                        p_e_w.p,    p_e_id.p, p_e_osym.p, p_st_ent.p};
   TPO = DecodePairOutTables{o_sym_seg.p,  o_seg_src.p,  o_seg_arc.p, o_m_dst.p, o_m_w.p,   o_m_id.p,    po_m_osym.p,
                             (uint32_t)h_polvl_ent.size() - 1, max_oseg, po_lvl_ent.p, po_ent_src.p, po_ent_arc.p, po_e_dst.p,
                             po_e_w.p, po_e_id.p, po_e_osym.p, po_eps_out.p};

@@ -1,5 +1,6 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
-// samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip and decode_pairs_posterior.hip) share: the prepared tables, the decoder
+// samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip and
+// decode_pairs_sample.hip) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built and
 // uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum share is
@@ -76,6 +77,7 @@ struct DecodePairTables {
   const double* e_w;
   const uint32_t* e_id;
   const uint32_t* e_osym;   // 0: a 00 arc (source in the same cell); else a 0M arc (source in cell (i, j - 1))
+  const uint32_t* st_ent;   // [n_states] -> the entry whose destination the state is (kNone: no such arc enters it); the pair sampler's walk
 };
 
 // The outgoing view of DecodePairTables, for the backward pass of the pair arc posteriors (decode_pairs_posterior.hip): an arc is
@@ -143,7 +145,7 @@ struct carmel_hip_decoder {
   DecodeOutTables TO;
   // the pair decoder's tables (decode_pairs.hip); pair_cycle: empty, or the 00 cycle that makes both pair entry points refuse
   std::vector<uint32_t> osym;  // the other side's symbol of every arc
-  DevBuf<uint32_t> p_m_osym, p_lvl_ent, p_ent_dst, p_ent_arc, p_e_src, p_e_id, p_e_osym;
+  DevBuf<uint32_t> p_m_osym, p_lvl_ent, p_ent_dst, p_ent_arc, p_e_src, p_e_id, p_e_osym, p_st_ent;
   DevBuf<double> p_e_w;
   DevBuf<uint8_t> a_flags;  // per arc, for the pair walk: bit 0 the matched symbol is not epsilon, bit 1 the other symbol is not
   DecodePairTables TP;
@@ -155,7 +157,7 @@ struct carmel_hip_decoder {
   uint32_t pair_levels = 0;  // the highest 00 level
   std::string pair_cycle;
   std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
-  // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample): every path's reported weight, the CSR
+  // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample, carmel_hip_decode_pairs_sample): every path's reported weight, the CSR
   // of the paths' arcs, the arcs
   std::vector<double> kb_logw;
   std::vector<uint64_t> kb_off;

@@ -44,35 +44,6 @@
 #include "decode_pairs_trellis.hpp"
 
 namespace {
-struct KeepOut {
-  const uint64_t* a_off;  // [n + 1]: each pair's (n + 1)(m + 1)|Q| doubles
-  double* alpha;
-};
-
-// SumAcc, and the closed diagonals kept
-struct KeepAcc {
-  typedef KeepOut Out;
-  static constexpr bool kKeep = true;
-  Lse a;
-  __device__ __forceinline__ void init(bool start) {
-    a.init();
-    if (start) a.add(0.0);
-  }
-  __device__ __forceinline__ void add(double x, uint32_t) { a.add(x); }
-  __device__ __forceinline__ double store(const Out&, uint32_t, size_t) const { return a.value(); }
-  static __device__ __forceinline__ void read_out(const Out&, uint32_t, double) {}  // (Z is the plane's last cell)
-  // cells (i, d - i), i = ilo .. ihi, of the closed diagonal `cur` -> the plane
-  static __device__ __forceinline__ void keep(const Out& O, uint32_t pair, const double* cur, uint32_t d, uint32_t ilo, uint32_t ihi,
-                                              bool by_i, uint32_t m, uint32_t Q, int lane) {
-    double* A = O.alpha + O.a_off[pair];
-    const uint64_t n_slot = ((uint64_t)(ihi - ilo) + 1) * Q;
-    for (uint64_t t = lane; t < n_slot; t += kLanes) {
-      const uint32_t i = ilo + (uint32_t)(t / Q), q = (uint32_t)(t % Q), j = d - i;
-      A[((size_t)i * (m + 1) + j) * Q + q] = cur[(size_t)(by_i ? i : j) * Q + q];
-    }
-  }
-};
-
 // what the backward kernel takes beside the tables and the pairs
 struct PairBack {
   const uint64_t* a_off;

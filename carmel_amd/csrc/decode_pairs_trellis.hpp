@@ -1,10 +1,12 @@
 // decode_pairs_trellis.hpp — what the pair entry points (decode_pairs.hip: the Viterbi alignment and the sum;
-// decode_pairs_posterior.hip: the arc posteriors) share: the anti-diagonal trellis over (matched position i, other position j,
-// state q) with its fixed candidate order, the sum's accumulator, and the host side of a call -- the argument checks, the tier
-// and the global tier's diagonals.  The trellis, its order and its barriers are described in decode_pairs.hip's header.
+// decode_pairs_posterior.hip: the arc posteriors; decode_pairs_sample.hip: the alignment samples) share: the anti-diagonal
+// trellis over (matched position i, other position j, state q) with its fixed candidate order, the sum's accumulator, the
+// accumulator that keeps every node (the forward pass of the posteriors and of the sampler), and the host side of a call -- the
+// argument checks, the tier and the global tier's diagonals.  The trellis, its order and its barriers are described in
+// decode_pairs.hip's header.
 //
 // An accumulator Acc gives init / add / store / read_out (decode_pairs.hip) and kKeep: if set, every closed diagonal is copied
-// out, cooperatively and after its last barrier, by Acc::keep -- the forward planes of the arc posteriors.
+// out, cooperatively and after its last barrier, by Acc::keep -- the forward planes of the arc posteriors and of the sampler.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -43,6 +45,35 @@ struct SumAcc {
   __device__ __forceinline__ void add(double x, uint32_t) { a.add(x); }
   __device__ __forceinline__ double store(const Out&, uint32_t, size_t) const { return a.value(); }
   static __device__ __forceinline__ void read_out(const Out& O, uint32_t pair, double f) { O.sum[pair] = f; }
+};
+
+struct KeepOut {
+  const uint64_t* a_off;  // [n + 1]: each pair's (n + 1)(m + 1)|Q| doubles
+  double* alpha;
+};
+
+// SumAcc, and the closed diagonals kept
+struct KeepAcc {
+  typedef KeepOut Out;
+  static constexpr bool kKeep = true;
+  Lse a;
+  __device__ __forceinline__ void init(bool start) {
+    a.init();
+    if (start) a.add(0.0);
+  }
+  __device__ __forceinline__ void add(double x, uint32_t) { a.add(x); }
+  __device__ __forceinline__ double store(const Out&, uint32_t, size_t) const { return a.value(); }
+  static __device__ __forceinline__ void read_out(const Out&, uint32_t, double) {}  // (Z is the plane's last cell)
+  // cells (i, d - i), i = ilo .. ihi, of the closed diagonal `cur` -> the plane
+  static __device__ __forceinline__ void keep(const Out& O, uint32_t pair, const double* cur, uint32_t d, uint32_t ilo, uint32_t ihi,
+                                              bool by_i, uint32_t m, uint32_t Q, int lane) {
+    double* A = O.alpha + O.a_off[pair];
+    const uint64_t n_slot = ((uint64_t)(ihi - ilo) + 1) * Q;
+    for (uint64_t t = lane; t < n_slot; t += kLanes) {
+      const uint32_t i = ilo + (uint32_t)(t / Q), q = (uint32_t)(t % Q), j = d - i;
+      A[((size_t)i * (m + 1) + j) * Q + q] = cur[(size_t)(by_i ? i : j) * Q + q];
+    }
+  }
 };
 
 // what a lane knows of the diagonal it works on

@@ -107,6 +107,8 @@ struct Options {
   bool have_pair_alignments = false;
   std::string pair_counts;       // --pair-counts=FILE: the composed machine with every arc's expected count over all derivations
   bool have_pair_counts = false;  // of the pairs as its weight (carmel_hip_decode_pairs_posterior), written to FILE
+  long pair_samples = 0;          // --pair-samples=N: N alignments per pair drawn from the posterior over the pair's derivations
+  bool have_pair_samples = false;  // (carmel_hip_decode_pairs_sample, seeded by -R), printed in place of the pair's best derivation
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };

@@ -24,6 +24,10 @@
 // of a pair's path only spell the two lines again.  --pair-counts=FILE is --posterior-counts=FILE for the pairs: the composed
 // machine, every arc's weight replaced by its expected number of uses over all derivations of the pairs, every pair weighing 1
 // (carmel_hip_decode_pairs_posterior, csrc/decode_pairs_posterior.hip: the E-step of carmel -t for these pairs).
+// --pair-samples=N is --sample-paths=N for the pairs: N derivations of every pair drawn from the posterior over the pair's
+// derivations, in sample order (carmel_hip_decode_pairs_sample, csrc/decode_pairs_sample.hip, seeded by -R), printed in place
+// of the best one with print_kbest's fill lines, N lines a pair; no Viterbi line is reported.  --pair-alignments=OUT then gets
+// one line per sample, N lines a pair (N empty lines for a pair without a derivation): sample s of pair l is line l N + s.
 #include <cctype>
 #include "carmel_cli.hpp"
 using namespace carmel_host;
@@ -124,8 +128,12 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   const size_t n = lines.size();
   line_paths.assign(n + 1, 0);
   const auto t0 = std::chrono::steady_clock::now();
-  if (o.have_kbest || o.have_sample) {
-    if (o.have_sample)
+  if (o.have_kbest || o.have_sample || o.have_pair_samples) {
+    if (o.have_pair_samples)
+      hip_check(carmel_hip_decode_pairs_sample(d, (uint32_t)kbest, o.seed, n, off.data(), sym.data(), off2.data(), sym2.data(),
+                                               line_paths.data()),
+                "carmel_hip_decode_pairs_sample");
+    else if (o.have_sample)
       hip_check(carmel_hip_decode_sample(d, (uint32_t)kbest, o.seed, n, off.data(), sym.data(), line_paths.data()),
                 "carmel_hip_decode_sample");
     else
@@ -159,7 +167,10 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   if (timing_on()) {
     double kms = 0;
     carmel_hip_decoder_last_ms(d, &kms);
-    std::cerr << (o.have_sample ? "timing: sample " : o.have_pair_lines ? "timing: pairs " : "timing: decode ")
+    std::cerr << (o.have_pair_samples ? "timing: pairs sample "
+                  : o.have_sample     ? "timing: sample "
+                  : o.have_pair_lines ? "timing: pairs "
+                                      : "timing: decode ")
               << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
               << " s (kernels " << kms * 1e-3 << " s)\n";
   }
@@ -204,18 +215,21 @@ void Batch::sum_paths(carmel_hip_decoder* d) {
     if (sums[l] > kNegInf) prod_sum += sums[l];
 }
 
-// every pair's best path as in:out symbol names, one line a pair
+// every pair's best path as in:out symbol names, one line a pair; with --pair-samples=N every sample, N lines a pair
 void Batch::pair_alignments() const {
+  const uint64_t per_pair = o.have_pair_samples ? (uint64_t)o.pair_samples : 1;
   std::string buf;
-  for (size_t l = 0; l < lines.size(); ++l) {
-    for (uint64_t p = line_paths[l]; p < line_paths[l + 1]; ++p)
-      for (uint64_t k = path_off[p]; k < path_off[p + 1]; ++k) {
-        const HArc& a = *arc_of[path[k]];
-        if (k > path_off[p]) buf += ' ';
-        buf += (a.in ? M.in_syms.names[a.in] : std::string("*e*")) + ":" + (a.out ? M.out_syms.names[a.out] : std::string("*e*"));
-      }
-    buf += '\n';
-  }
+  for (size_t l = 0; l < lines.size(); ++l)
+    for (uint64_t r = 0; r < per_pair; ++r) {  // (a pair without a derivation: empty lines)
+      const uint64_t p = line_paths[l] + r;
+      if (p < line_paths[l + 1])
+        for (uint64_t k = path_off[p]; k < path_off[p + 1]; ++k) {
+          const HArc& a = *arc_of[path[k]];
+          if (k > path_off[p]) buf += ' ';
+          buf += (a.in ? M.in_syms.names[a.in] : std::string("*e*")) + ":" + (a.out ? M.out_syms.names[a.out] : std::string("*e*"));
+        }
+      buf += '\n';
+    }
   std::ofstream of(o.pair_alignments.c_str());
   of << buf;
   of.close();
@@ -351,7 +365,7 @@ void Batch::report() const {
     std::cerr << "No derivations found for " << n_0prob << " of " << n << " inputs.\n";
   else
     std::cerr << "Derivations found for all " << n << " inputs.\n";
-  if (!o.have_sample) {  // (sampling computes no best path)
+  if (!o.have_sample && !o.have_pair_samples) {  // (sampling computes no best path)
     std::cerr << "Viterbi (best path) ";
     log_ppx(n_prob, prod_viterbi, n_0prob);
   }
@@ -383,7 +397,10 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
     carmel_hip_decoder* d;
     ~Guard() { carmel_hip_decoder_destroy(d); }
   } guard{d};
-  const size_t kbest = o.have_sample ? (size_t)o.sample_paths : o.have_kbest ? (size_t)o.kbest : 1;  // output lines per input line
+  const size_t kbest = o.have_pair_samples ? (size_t)o.pair_samples
+                       : o.have_sample     ? (size_t)o.sample_paths
+                       : o.have_kbest      ? (size_t)o.kbest
+                                           : 1;  // output lines per input line
   b.decode(d, kbest);
   if (o.sum) b.sum_paths(d);
   if (o.have_posterior) b.posterior_counts(d);

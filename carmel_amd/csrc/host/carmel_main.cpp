@@ -35,7 +35,9 @@ static int print_help() {
                "pair decoding: --pair-lines=FILE with -b / -i and -k 1 (carmel's --post-b=FILE: line k of FILE is the other side of line k) "
                "prints every pair's best derivation, --sum-paths then multiplies the pairs' sums, --pair-alignments=OUT writes "
                "the best paths as in:out symbol pairs, --pair-counts=FILE writes the composed machine with every arc's expected "
-               "count over all derivations of the pairs as its weight (no cycles of *e*:*e* arcs); "
+               "count over all derivations of the pairs as its weight (no cycles of *e*:*e* arcs), --pair-samples=N (N <= 65536) "
+               "prints N alignments of every pair drawn from the posterior over its derivations in place of the best one, seeded "
+               "by -R, and --pair-alignments=OUT then gets one line per sample; "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -53,6 +55,15 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
     if (o.pair_counts.empty()) throw UsageError("--pair-counts=FILE needs a file name");
     if (with_pairs || o.train_cascade) throw UsageError("--pair-counts=FILE with -t / --train-cascade / -S is not implemented");
     if (!o.have_pair_lines) throw UsageError("--pair-counts=FILE needs --pair-lines=FILE");
+  }
+  if (o.have_pair_samples) {
+    if (with_pairs || o.train_cascade) throw UsageError("--pair-samples=N with -t / --train-cascade / -S is not implemented");
+    if (!o.have_pair_lines) throw UsageError("--pair-samples=N needs --pair-lines=FILE");
+    if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i']) throw UsageError("--pair-samples=N applies to batch decoding (-b or -i)");
+    if (o.have_kbest) throw UsageError("--pair-samples=N and --kbest=N exclude each other");
+    if (o.have_sample) throw UsageError("--pair-samples=N and --sample-paths=N exclude each other");
+    if (o.pair_samples < 1 || o.pair_samples > 65536) throw UsageError("--pair-samples=N needs 1 <= N <= 65536");
+    if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.pair_samples) throw UsageError("--pair-samples=N with -k m: m must be 1 or N");
   }
   if (o.have_pair_alignments && !o.have_pair_lines) throw UsageError("--pair-alignments=OUT needs --pair-lines=FILE");
   if (o.have_pair_lines) {
@@ -73,7 +84,7 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
     } else if (o.have_kbest) {
       if (o.kbest < 1 || o.kbest > 1024) throw UsageError("--kbest=N needs 1 <= N <= 1024");
       if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.kbest) throw UsageError("--kbest=N with -k m: m must be 1 or N");
-    } else {
+    } else if (!o.have_pair_samples) {  // (--pair-samples=N: -k is absent, 1 or N, checked above)
       if (o.kpaths > 1)
         throw UsageError("-k n with n > 1 (k-best paths) is not implemented; -k 1 with -b or -i is; use --kbest=n");
       if (o.kpaths < 1) throw UsageError("-b / -i without -k 1 (printing each line's composition) is not implemented");

@@ -134,6 +134,10 @@ Options parse_args(int argc, char** argv) {
         o.pair_counts = v;
         o.have_pair_counts = true;
       }
+      else if (k == "pair-samples") {  // not a carmel option: N posterior samples of every pair's derivations (carmel_hip_decode_pairs_sample)
+        o.pair_samples = std::atol(v.c_str());
+        o.have_pair_samples = true;
+      }
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")

@@ -11,6 +11,7 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     best, paths = d.decode_pairs(lines, lines2)    # lines2: the other side's line of every pair (carmel --post-b=FILE)
     sums = d.sum_pairs(lines, lines2)              # ln of every pair's sum over all its derivations (csrc/decode_pairs.hip)
     sums, counts = d.posterior_pairs(lines, lines2, weights=None)   # expected uses of every arc over the pairs' derivations
+    weights, spaths = d.sample_pairs(lines, lines2, n, seed=0)      # n derivations per pair, each drawn with probability weight / sum
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -23,7 +24,10 @@ backward trellis); the sums are fixed to the bit, the counts up to the order of 
 A pair (lines[l], lines2[l]) is a line of the decoder's side and a line of the other side, in that side's alphabet; its
 derivations spell both.  decode_pairs returns decode's shapes (the Viterbi alignment of every pair), sum_pairs sum's, and
 posterior_pairs posterior's: sum_pairs' sums, bit for bit, and the arcs' expected uses over the pairs' derivations
-(csrc/decode_pairs_posterior.hip: the pair trellis forwards and backwards)."""
+(csrc/decode_pairs_posterior.hip: the pair trellis forwards and backwards).  sample_pairs returns sample's shapes: a pair with a
+derivation has exactly n alignments, in sample order, duplicates kept, each drawn from the posterior over the pair's derivations;
+sample s of pair l depends on the machine, the pair, the seed, l and s alone (csrc/decode_pairs_sample.hip: the forward planes of
+the arc posteriors and a backward sampling walk); sample_pairs_raw returns sample_raw's flat arrays."""
 import ctypes as C
 
 import numpy as np
@@ -148,6 +152,20 @@ class Decoder(object):
         check(lib.carmel_hip_decode_pairs_posterior(self._h, len(lines), ptr(off), ptr(sym), ptr(off2), ptr(sym2), ptr(wt), ptr(sums),
                                                     ptr(counts)), "carmel_hip_decode_pairs_posterior")
         return sums, counts[:self.n_arcs]
+
+    def sample_pairs_raw(self, lines, lines2, n, seed=0):
+        """-> (line_paths, logw, path_off, arcs): the arrays of carmel_hip_decode_pairs_sample / carmel_hip_decoder_get_kbest"""
+        assert len(lines) == len(lines2)
+        off, sym = _pack(lines)
+        off2, sym2 = _pack(lines2)
+        line_paths = np.zeros(len(lines) + 1, np.uint64)
+        check(lib.carmel_hip_decode_pairs_sample(self._h, int(n), int(seed), len(lines), ptr(off), ptr(sym), ptr(off2), ptr(sym2),
+                                                 ptr(line_paths)), "carmel_hip_decode_pairs_sample")
+        return self._last_paths(line_paths)
+
+    def sample_pairs(self, lines, lines2, n, seed=0):
+        """-> (weights, paths) shaped as sample's: per pair its n sampled derivations (none: no derivation)"""
+        return self._per_line(len(lines), *self.sample_pairs_raw(lines, lines2, n, seed))
 
     def posterior(self, lines, weights=None):
         """-> (sums, counts): sum(lines), and per arc its expected number of uses over the derivations of the lines (line l counts

@@ -662,6 +662,33 @@ int carmel_hip_decode_pairs_sum(carmel_hip_decoder* d, uint64_t n_pairs, const u
 int carmel_hip_decode_pairs_posterior(carmel_hip_decoder* d, uint64_t n_pairs, const uint64_t* off, const uint32_t* sym,
                                       const uint64_t* off2, const uint32_t* sym2, const double* pair_weight /* nullable */,
                                       double* sum_logw /* [n_pairs], nullable */, double* arc_count /* [n_arcs], overwritten */);
+/* ---- batch pair alignment sampling (csrc/decode_pairs_sample.hip) ----
+ * Stands beside carmel_hip_decode_pairs (the Viterbi alignment) and carmel_hip_decode_pairs_sum (the weight of all) over the
+ * pairs of carmel's --post-b=FILE (carmel.cc:569-597): for every pair, n_samples derivations drawn independently with
+ * probability w(d) / (the sum over all derivations of the pair).  It replaces nothing of the reference, which has no sampler
+ * over a fixed machine outside its --crp trainer.  Pairs and derivations as carmel_hip_decode_pairs defines them.  A pair
+ * without a derivation gets no paths, every other pair exactly n_samples -- paths line_paths[l] .. line_paths[l + 1]
+ * (line_paths: n_pairs + 1 entries) of carmel_hip_decoder_kbest_size / carmel_hip_decoder_get_kbest, exactly as after
+ * carmel_hip_decode_sample -- in sample order, duplicates kept; a path's reported weight is its arcs' logs added from the END.
+ * The forward pass is carmel_hip_decode_pairs_posterior's: alpha[i][j][q] over (position in x, position in y, state), every node
+ * kept, alpha[n][m][final] bit for bit carmel_hip_decode_pairs_sum's value; a pair has a derivation iff that is > -inf.
+ * Sample s of pair l (l: the pair's index in THIS call) starts at (i, j, q) = (n, m, final) with step = 0.  At (i, j, q) the
+ * candidates are, in this order: "stop", value 0.0, at (0, 0, 0) only; if i > 0 the arcs into q whose matched symbol is x_i, in
+ * arc-id order, an arc whose other symbol is epsilon with value alpha[i-1][j][src] + w, any other only if j > 0 and its other
+ * symbol is y_j, with value alpha[i-1][j-1][src] + w; then the arcs into q whose matched symbol is epsilon, in arc-id order, an
+ * arc with epsilon on both sides with value alpha[i][j][src] + w, any other only if j > 0 and its other symbol is y_j, with
+ * value alpha[i][j-1][src] + w.  With Z = alpha[i][j][q]: p_c = exp(value_c - Z), 0 for -inf; S = the p_c added in candidate
+ * order in f64; u = carmel_hip_gibbs_uniform(seed, s, l, step); t = u S.  The first candidate with p_c > 0 whose running sum
+ * exceeds t is chosen, else the last candidate with p_c > 0.  "Stop" ends the walk; otherwise the arc is prepended, step is
+ * incremented, q becomes the arc's source, i drops if the arc's matched symbol is not epsilon and j if its other symbol is not.
+ * So a sample depends on the machine, the weights, the side, its pair, the seed, l and s alone: not on chunking, memory tier,
+ * launch order or the other pairs.  1 <= n_samples <= 65536, a null d, off, off2 or line_paths, bad offsets on either side, or
+ * n_pairs >= 2^32: CARMEL_HIP_ERR_ARG.  An insertion loop *e*:y is legal; a cycle of arcs with epsilon on both sides fails with
+ * CARMEL_HIP_ERR_UNSUPPORTED, naming the cycle, nothing is written and the handle stays usable.  May alternate with the other
+ * decode entry points on one handle, and sees the weights of carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers
+ * the forward kernel and both passes of the walk. */
+int carmel_hip_decode_pairs_sample(carmel_hip_decoder* d, uint32_t n_samples, uint64_t seed, uint64_t n_pairs, const uint64_t* off,
+                                   const uint32_t* sym, const uint64_t* off2, const uint32_t* sym2, uint64_t* line_paths);
 
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */

@@ -23,10 +23,15 @@ carmel_hip_decode_pairs_sum timed in the same loop ("pairs_posterior": kernel an
 time as a multiple of the pair sum's, whether the sums are the pair sum's bit for bit, the matched and the other-side arcs' counts
 against the lengths of the pairs with a derivation), and writes that run's figures to --pairs-posterior-out
 (profiles/decode_pairs_posterior_bench.json).
+--pairs-sample[=N] (N = 8 if left out) adds the same pairs through carmel_hip_decode_pairs_sample (csrc/decode_pairs_sample.hip)
+with N samples a pair (seed 1), beside carmel_hip_decode_pairs_sum and carmel_hip_decode_pairs_posterior timed in the same loop
+("pairs_sample": kernel and call time of the three, pairs per second, the sampler's kernels' time as a multiple of the pair sum's
+and of the pair posteriors', the memory tier, whether every pair with a sum has N paths and every path spells its pair), and
+writes that run's figures to --pairs-sample-out (profiles/decode_pairs_sample_bench.json).
 Prints one JSON object.
 
     python tools/decode_bench.py [--lines 100000] [--reps 5] [--fst tests/golden/tagging.fst] [--kbest 1 --kbest 4 ...] [--sum]
-                                 [--sample 1 --sample 16] [--posterior] [--pairs] [--pairs-posterior]
+                                 [--sample 1 --sample 16] [--posterior] [--pairs] [--pairs-posterior] [--pairs-sample[=N]]
 
 The tagging fst defaults to the untrained tests/golden/tagging.fst (same arcs as the trained one: the timing does not depend
 on the weights); the cluster and cipher commands use their committed trained members."""
@@ -71,6 +76,8 @@ def main():
     ap.add_argument("--pairs-out", default=os.path.join(ROOT, "profiles", "decode_pairs_bench.json"))
     ap.add_argument("--pairs-posterior", action="store_true")
     ap.add_argument("--pairs-posterior-out", default=os.path.join(ROOT, "profiles", "decode_pairs_posterior_bench.json"))
+    ap.add_argument("--pairs-sample", type=int, nargs="?", const=8, default=None, metavar="N")
+    ap.add_argument("--pairs-sample-out", default=os.path.join(ROOT, "profiles", "decode_pairs_sample_bench.json"))
     a = ap.parse_args()
     sample_ns = a.sample + ([1] if a.posterior and 1 not in a.sample else [])  # (the posteriors are reported beside one sample a line)
     from carmel_amd.decode import Decoder
@@ -204,6 +211,48 @@ def main():
         for v in (ppost["sum"], ppost["posterior"]):
             v["pairs_per_s"] = len(lines) / (v["kernel_ms"] * 1e-3)
         ppost["posterior"]["kernel_ms_over_pair_sum"] = ppost["posterior"]["kernel_ms"] / ppost["sum"]["kernel_ms"]
+    psamp = None
+    if a.pairs_sample:
+        N = a.pairs_sample
+        isym, osym = np.asarray(w["isym"]), np.asarray(w["osym"])
+        other = [isym[p][isym[p] != 0] for p in paths]  # the tags of the line's best path
+        d.sum_pairs(lines[:1000], other[:1000])
+        d.posterior_pairs(lines[:1000], other[:1000])
+        d.sample_pairs_raw(lines[:1000], other[:1000], N, 1)
+        kms_t, wall_t, kms_p, wall_p, kms_n, wall_n = [], [], [], [], [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            psum = d.sum_pairs(lines, other)
+            wall_t.append((time.perf_counter() - t0) * 1e3)
+            kms_t.append(d.last_ms())
+            t0 = time.perf_counter()
+            d.posterior_pairs(lines, other)
+            wall_p.append((time.perf_counter() - t0) * 1e3)
+            kms_p.append(d.last_ms())
+            t0 = time.perf_counter()
+            line_paths, logw, path_off, arcs = d.sample_pairs_raw(lines, other, N, 1)
+            wall_n.append((time.perf_counter() - t0) * 1e3)
+            kms_n.append(d.last_ms())
+        with_paths = np.diff(line_paths) > 0
+        # every sampled path spells its pair: its arcs' non-epsilon symbols, side by side, against the pairs' symbols repeated N times
+        a64 = arcs.astype(np.int64)
+        rep = lambda seqs: np.concatenate([np.tile(np.asarray(x, np.int64), N) for x, h in zip(seqs, with_paths) if h] + [np.zeros(0, np.int64)])
+        spelt = bool(np.array_equal(osym[a64][osym[a64] != 0], rep(lines)) and np.array_equal(isym[a64][isym[a64] != 0], rep(other)))
+        longest = max(min(len(x), len(y)) + 1 for x, y in zip(lines, other)) * int(w["n_states"])
+        psamp = {"n_samples": N,
+                 "sum": {"kernel_ms": float(np.median(kms_t)), "kernel_ms_all": kms_t, "call_ms": float(np.median(wall_t))},
+                 "posterior": {"kernel_ms": float(np.median(kms_p)), "kernel_ms_all": kms_p, "call_ms": float(np.median(wall_p))},
+                 "sample": {"kernel_ms": float(np.median(kms_n)), "kernel_ms_all": kms_n, "call_ms": float(np.median(wall_n))},
+                 "trellis_nodes": int(sum((len(x) + 1) * (len(y) + 1) for x, y in zip(lines, other))) * int(w["n_states"]),
+                 "tier": "lds" if 3 * longest <= 8192 else "global",  # (decided by the call's longest pair: decode_pairs.hip)
+                 "paths": int(len(logw)), "path_arcs": int(len(arcs)),
+                 "every_pair_with_a_sum_has_n_paths": bool(np.array_equal(with_paths, ~np.isneginf(psum)) and
+                                                           (np.diff(line_paths)[with_paths] == N).all()),
+                 "every_path_spells_its_pair": spelt}
+        for v in (psamp["sum"], psamp["posterior"], psamp["sample"]):
+            v["pairs_per_s"] = len(lines) / (v["kernel_ms"] * 1e-3)
+        psamp["sample"]["kernel_ms_over_pair_sum"] = psamp["sample"]["kernel_ms"] / psamp["sum"]["kernel_ms"]
+        psamp["sample"]["kernel_ms_over_pair_posterior"] = psamp["sample"]["kernel_ms"] / psamp["posterior"]["kernel_ms"]
     d.close()
     n_pos = int(sum(len(x) for x in lines))
     # matched relaxations: for every position, the arcs whose output is that symbol (each one add + compare)
@@ -270,6 +319,12 @@ def main():
         with open(a.pairs_posterior_out, "w") as f:
             json.dump({"workload": res["workload"] + ", every line paired with the tags of its best path", "machine": res["machine"],
                        "reps": a.reps, "pairs_posterior": ppost}, f)
+            f.write("\n")
+    if psamp:
+        res["pairs_sample"] = psamp
+        with open(a.pairs_sample_out, "w") as f:
+            json.dump({"workload": res["workload"] + ", every line paired with the tags of its best path", "machine": res["machine"],
+                       "reps": a.reps, "pairs_sample": psamp}, f)
             f.write("\n")
     if a.sum:
         with open(a.sum_out, "w") as f:
