@@ -937,6 +937,10 @@ void trans_args(carmel_hip_trainer* t, TransArgs& T) {
   T.bucket_count = T.n_buckets;
   T.n_wtiles = 0;
   T.slack_bytes = (uint32_t)DEVBUF_SLACK;  // x, xc, t_pos, t_src are DevBufs
+  // the count pass's bucket kernel as a walk of a workgroup per CU over the buckets (kernels.hip: bucket_walk_at); "0": a
+  // workgroup per bucket (A/B, bit-identical results); N: at most N workgroups
+  T.bucket_walk = TRANS_WALK_AUTO;
+  if (const char* e = lib_opt("trans_bucket_walk")) T.bucket_walk = (uint32_t)std::max(0, atoi(e));
 }
 
 // CARMEL_HIP_POISON=2 (debugging): LDS keeps what the last workgroup on the CU left there -- zeros on an idle box, somebody's

@@ -706,13 +706,26 @@ __global__ __launch_bounds__(256) void scalars_partial_kernel(const double* __re
                                                               double* __restrict__ partial) {
   __shared__ double sh[3][4];
   double a = 0.0, b = 0.0, c = 0.0;
-  for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < n_pairs; p += (uint64_t)SCALAR_BLOCKS * 256) {
-    const double w = pair_w[p];
-    if (w < 0.0) continue;
-    const double lp = pair_logprob[p];
-    a += lp;
-    b += lp * w;
-    c += 1.0;
+  // a thread's loads are issued SCALAR_ROUNDS rounds at a time, both arrays, before anything is added (a dropped pair's ln p
+  // is read and not used): one round trip per batch, not two dependent ones per pair.  The additions are the same, in the same
+  // order, under the same condition.
+  constexpr int SCALAR_ROUNDS = 16;
+  constexpr uint64_t STRIDE = (uint64_t)SCALAR_BLOCKS * 256;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256 + threadIdx.x; p0 < n_pairs; p0 += STRIDE * SCALAR_ROUNDS) {
+    double w[SCALAR_ROUNDS], lp[SCALAR_ROUNDS];
+#pragma unroll
+    for (int k = 0; k < SCALAR_ROUNDS; ++k) {
+      const uint64_t p = p0 + k * STRIDE;
+      w[k] = p < n_pairs ? pair_w[p] : -1.0;
+      lp[k] = p < n_pairs ? pair_logprob[p] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < SCALAR_ROUNDS; ++k) {
+      if (w[k] < 0.0) continue;
+      a += lp[k];
+      b += lp[k] * w[k];
+      c += 1.0;
+    }
   }
   for (int o = 32; o > 0; o >>= 1) {
     a += __shfl_down(a, o, 64);
@@ -1166,18 +1179,9 @@ __device__ __forceinline__ RunLds run_lds(double* after_tile) {
   R.pref = R.mask + TRANS_RUN_WORDS;
   return R;
 }
-// (called by all 1024 threads; contains barriers)
-__device__ __forceinline__ void run_stage(const RunLds& R, const uint16_t* __restrict__ rel, const uint32_t* __restrict__ src,
-                                          uint32_t nr) {
+// the prefix counts of the mask words (the first wavefront)
+__device__ __forceinline__ void run_prefix(const RunLds& R) {
   constexpr uint32_t WORDS = TRANS_RUN_WORDS, PER = WORDS / 64;
-  for (uint32_t w = threadIdx.x; w < WORDS; w += 1024) R.mask[w] = 0u;
-  __syncthreads();
-  for (uint32_t r = threadIdx.x; r < nr; r += 1024) {
-    const uint32_t first = rel[r];
-    R.r_src[r] = src[r] - first;
-    atomicOr(&R.mask[first >> 5], 1u << (first & 31u));
-  }
-  __syncthreads();
   if (threadIdx.x < 64) {
     uint32_t c[PER], tot = 0;
 #pragma unroll
@@ -1195,12 +1199,112 @@ __device__ __forceinline__ void run_stage(const RunLds& R, const uint16_t* __res
 #pragma unroll
     for (uint32_t k = 0; k < PER; ++k) R.pref[threadIdx.x * PER + k] = before + c[k];
   }
+}
+// (called by all 1024 threads; contains barriers)
+__device__ __forceinline__ void run_stage(const RunLds& R, const uint16_t* __restrict__ rel, const uint32_t* __restrict__ src,
+                                          uint32_t nr) {
+  for (uint32_t w = threadIdx.x; w < TRANS_RUN_WORDS; w += 1024) R.mask[w] = 0u;
+  __syncthreads();
+  for (uint32_t r = threadIdx.x; r < nr; r += 1024) {
+    const uint32_t first = rel[r];
+    R.r_src[r] = src[r] - first;
+    atomicOr(&R.mask[first >> 5], 1u << (first & 31u));
+  }
+  __syncthreads();
+  run_prefix(R);
+  __syncthreads();
+}
+// ... the same from registers: a bucket pass asks for its runs with its first batch of loads (they depend on nothing but
+// the bucket number) instead of behind the first barrier here, where they were a round trip of their own.  At most
+// TRANS_RUN_CAP runs (TransArgs::use_runs): RUN_K rounds of 1024 threads, thread t holding runs t, t + 1024, ...
+#define RUN_K (TRANS_RUN_CAP / 1024)
+struct RunRegs {
+  uint32_t first[RUN_K], src[RUN_K];
+};
+__device__ __forceinline__ RunRegs run_request(const uint16_t* __restrict__ rel, const uint32_t* __restrict__ src, uint32_t nr) {
+  RunRegs q;
+#pragma unroll
+  for (int k = 0; k < RUN_K; ++k) {
+    const uint32_t r = threadIdx.x + k * 1024;
+    q.first[k] = r < nr ? (uint32_t)rel[r] : 0u;
+    q.src[k] = r < nr ? src[r] : 0u;
+  }
+  return q;
+}
+// (called by all 1024 threads; contains barriers)
+__device__ __forceinline__ void run_stage(const RunLds& R, const RunRegs& q, uint32_t nr) {
+  for (uint32_t w = threadIdx.x; w < TRANS_RUN_WORDS; w += 1024) R.mask[w] = 0u;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < RUN_K; ++k) {
+    const uint32_t r = threadIdx.x + k * 1024;
+    if (r < nr) {
+      R.r_src[r] = q.src[k] - q.first[k];
+      atomicOr(&R.mask[q.first[k] >> 5], 1u << (q.first[k] & 31u));
+    }
+  }
+  __syncthreads();
+  run_prefix(R);
   __syncthreads();
 }
 __device__ __forceinline__ uint32_t run_source(const RunLds& R, uint32_t i) {
   const uint32_t w = i >> 5;
   const uint32_t run = R.pref[w] + __popc(R.mask[w] & (0xffffffffu >> (31u - (i & 31u)))) - 1u;
   return R.r_src[run] + i;
+}
+// The walk of the count pass over its buckets (TransArgs::bucket_walk; trans_c_bucket_kernel<.., WALK>): a grid of at most a
+// workgroup per CU, workgroup b on XCD b % 8 taking the buckets of that XCD's contiguous eighth (xcd_chunked) a grid apart.
+// The descriptor of the NEXT bucket (and where its runs
+// lie) is requested while this one is worked on: through an address the compiler cannot prove uniform, so that it stays a
+// pending vector load until bw_uniform makes it scalar at its use (tile_sweep.hip: ts_zero / ts_sc) -- a uniform load would
+// be waited for where it is issued.
+__device__ __forceinline__ uint32_t bw_zero() {
+  uint32_t z = 0;
+  asm volatile("" : "+v"(z));
+  return z;
+}
+// (a thread's number the compiler cannot see through: inside the walk's loop, what is derived from it -- sixteen item offsets,
+// their addresses -- is worked out per bucket instead of being parked in registers around the loop, which took two of the
+// count pass's forms past the 128 registers a thread of a 1024-thread workgroup has)
+__device__ __forceinline__ uint32_t bw_opaque(uint32_t v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ uint32_t bw_sc(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+struct BucketWalk {
+  uint32_t bucket;  // (the range's first bucket when !ok: every request of a descriptor is of a bucket that exists)
+  bool ok;
+};
+__device__ __forceinline__ BucketWalk bucket_walk_at(const TransArgs& T, uint32_t vidx) {
+  BucketWalk w;
+  const uint32_t bloc = xcd_chunked(vidx, T.bucket_count);
+  // (vidx / 8 beyond an eighth would be a bucket of the next XCD's share)
+  w.ok = bloc < T.bucket_count && (vidx >> 3) < (T.bucket_count + 7) / 8;
+  w.bucket = T.bucket_first + (w.ok ? bloc : 0u);
+  return w;
+}
+struct BucketAhead {  // as loaded
+  TransBucket B;
+  uint32_t r0, r1;  // its runs: br_rel / br_src [r0, r1)
+};
+template <bool RUNS>
+__device__ __forceinline__ BucketAhead bucket_request(const TransArgs& T, uint32_t bucket, uint32_t z) {
+  BucketAhead a;
+  a.B = T.buckets[bucket + z];
+  a.r0 = RUNS ? T.br_off[bucket + z] : 0u;
+  a.r1 = RUNS ? T.br_off[bucket + 1 + z] : 0u;
+  return a;
+}
+__device__ __forceinline__ BucketAhead bw_uniform(const BucketAhead& v) {
+  BucketAhead a;
+  a.B.item_base = ((uint64_t)bw_sc((uint32_t)(v.B.item_base >> 32)) << 32) | bw_sc((uint32_t)v.B.item_base);
+  a.B.n_items = bw_sc(v.B.n_items);
+  a.B.arc_lo = bw_sc(v.B.arc_lo);
+  a.B.n_arcs = bw_sc(v.B.n_arcs);
+  a.B.flags = bw_sc(v.B.flags);
+  a.r0 = bw_sc(v.r0);
+  a.r1 = bw_sc(v.r1);
+  return a;
 }
 // weights, pass 1: one workgroup per arc bucket.  The bucket's weights go to LDS (coalesced read), its items leave in
 // position-sorted order (coalesced write), picking their weight out of LDS.
@@ -1218,6 +1322,11 @@ __global__ __launch_bounds__(1024) void trans_w_bucket_kernel(TransArgs T) {
   }
   const uint32_t bucket = T.bucket_first + bloc;
   const TransBucket B = T.buckets[bucket];
+  uint32_t run0 = 0, nr = 0;  // (asked for with the descriptor)
+  if (SC && RL) {
+    run0 = T.br_off[bucket];
+    nr = T.br_off[bucket + 1] - run0;
+  }
   // every loop below is a fixed 16 x 1024 sweep with its loads issued as one batch (a bucket / tile holds at most
   // 16384 items): one dependent round trip per phase instead of one per iteration
   double w[KB];
@@ -1234,12 +1343,13 @@ __global__ __launch_bounds__(1024) void trans_w_bucket_kernel(TransArgs T) {
     ia[k] = j < B.n_items ? T.b_arc[B.item_base + j] : (uint16_t)0;
     if (SC && !RL) dst[k] = j < B.n_items ? T.b_src[B.item_base + j] : 0u;
   }
+  RunRegs runs;  // (with the same batch: they depend on the bucket number alone)
+  if (SC && RL) runs = run_request(T.br_rel + run0, T.br_src + run0, nr);
 #pragma unroll
   for (int k = 0; k < KB; ++k) lds[threadIdx.x + k * 1024] = w[k];
-  if (SC && RL) {
-    const uint32_t r0 = T.br_off[bucket];
-    run_stage(R, T.br_rel + r0, T.br_src + r0, T.br_off[bucket + 1] - r0);
-  } else
+  if (SC && RL)
+    run_stage(R, runs, nr);
+  else
     __syncthreads();
 #pragma unroll
   for (int k = 0; k < KB; ++k) {
@@ -1434,107 +1544,135 @@ __global__ __launch_bounds__(TRANS_SMALL_THREADS) void trans_c_tile_small_kernel
 // then one thread per arc adds up its contiguous range in a fixed order -- no atomics, bit-reproducible.  A bucket
 // that is a piece of a split arc reduces the piece and adds it atomically.
 // SQ: pass 1 scattered (trans_c_tile_kernel<true, ..>): the bucket's items are xc[item_base .. ) in item order.
-template <bool RL, bool SQ, int KB = TRANS_KB>
+// WALK: the persistent form (bucket_walk_at): a workgroup takes bucket after bucket, a grid apart.
+template <bool RL, bool SQ, int KB = TRANS_KB, bool WALK = false>
 __global__ __launch_bounds__(1024) void trans_c_bucket_kernel(TransArgs T) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const RunLds R = run_lds(lds + KB * 1024);
   __shared__ double part[16];
   __shared__ uint32_t big[512];
   __shared__ uint32_t n_big;
-  const uint32_t bloc = xcd_chunked(blockIdx.x, T.bucket_count);  // the grid is rounded up to a multiple of 8
-  if (bloc >= T.bucket_count) return;
-  const uint32_t bucket = T.bucket_first + bloc;
-  const TransBucket B = T.buckets[bucket];
-  // every global load of the workgroup is issued before the first barrier: item indices, the items, and the item
-  // ranges of this thread's arcs (the per-arc loop below then runs out of registers and LDS alone)
-  uint16_t r0[KB], r1[KB];
-  const bool single = (B.flags & TRANS_SINGLE) != 0;
-#pragma unroll
-  for (int k = 0; k < KB; ++k) {
-    const uint32_t a = threadIdx.x + k * 1024;
-    const bool ok = !single && a < B.n_arcs;
-    r0[k] = ok ? T.a_off[B.arc_lo + a] : (uint16_t)0;
-    r1[k] = (ok && a + 1 < B.n_arcs) ? T.a_off[B.arc_lo + a + 1] : (uint16_t)0;
-  }
-  {
-    uint32_t src[KB];
-    uint16_t rk[KB];
-    double v[KB];
-    if (RL && !SQ) {
-      const uint32_t r0 = T.br_off[bucket];
-      run_stage(R, T.br_rel + r0, T.br_src + r0, T.br_off[bucket + 1] - r0);
+  const uint32_t z = WALK ? bw_zero() : 0u;
+  uint32_t vidx = blockIdx.x;
+  BucketWalk cur = bucket_walk_at(T, vidx);  // the grid is rounded up to a multiple of 8
+  if (!cur.ok) return;                             // grid padding: leaves before any barrier
+  BucketAhead A = bw_uniform(bucket_request<RL && !SQ>(T, cur.bucket, z));
+  for (;;) {
+    const TransBucket B = A.B;
+    const uint32_t tx = WALK ? bw_opaque(threadIdx.x) : threadIdx.x;
+    BucketWalk nxt = cur;
+    nxt.ok = false;
+    BucketAhead raw;
+    if (WALK) {  // the next bucket's descriptor is on its way while this bucket's loads are
+      nxt = bucket_walk_at(T, vidx + gridDim.x);
+      raw = bucket_request<RL && !SQ>(T, nxt.bucket, z);
     }
+    // every global load of the workgroup is issued before the first barrier: item indices, the items, and the item
+    // ranges of this thread's arcs (the per-arc loop below then runs out of registers and LDS alone)
+    // (an arc's first item and the next arc's in ONE load of four bytes at a two-byte boundary, and one register: behind the
+    // bucket's last arc that is the next bucket's first, not used, and behind the model's last arc two bytes of a_off's slack,
+    // DEVBUF_SLACK -- TransArgs::slack_bytes)
+    uint32_t r01[KB];
+    const bool single = (B.flags & TRANS_SINGLE) != 0;
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
-      const uint32_t j = threadIdx.x + k * 1024;
-      if (SQ)
-        src[k] = 0u;
-      else if (RL)
-        src[k] = j < B.n_items ? run_source(R, j) : 0u;
-      else
-        src[k] = j < B.n_items ? T.b_src[B.item_base + j] : 0u;
-      rk[k] = j < B.n_items ? T.b_rank[B.item_base + j] : (uint16_t)0;
+      const uint32_t a = tx + k * 1024;
+      r01[k] = 0u;
+      if (!single && a < B.n_arcs) __builtin_memcpy(&r01[k], T.a_off + B.arc_lo + a, 4);
     }
+    {
+      uint32_t src[KB];
+      uint16_t rk[KB];
+      double v[KB];
 #pragma unroll
-    for (int k = 0; k < KB; ++k) {
-      if (SQ) {
-        const uint32_t j = threadIdx.x + k * 1024;
-        v[k] = j < B.n_items ? T.xc[B.item_base + j] : 0.0;
-      } else
-        v[k] = T.xc[src[k]];
+      for (int k = 0; k < KB; ++k) {
+        const uint32_t j = tx + k * 1024;
+        rk[k] = j < B.n_items ? T.b_rank[B.item_base + j] : (uint16_t)0;
+      }
+      if (RL && !SQ) {  // (the runs with the same batch: they depend on the bucket number alone)
+        const RunRegs runs = run_request(T.br_rel + A.r0, T.br_src + A.r0, A.r1 - A.r0);
+        run_stage(R, runs, A.r1 - A.r0);
+      }
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        const uint32_t j = tx + k * 1024;
+        if (SQ)
+          src[k] = 0u;
+        else if (RL)
+          src[k] = j < B.n_items ? run_source(R, j) : 0u;
+        else
+          src[k] = j < B.n_items ? T.b_src[B.item_base + j] : 0u;
+      }
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        if (SQ) {
+          const uint32_t j = tx + k * 1024;
+          v[k] = j < B.n_items ? T.xc[B.item_base + j] : 0.0;
+        } else
+          v[k] = T.xc[src[k]];
+      }
+#pragma unroll
+      for (int k = 0; k < KB; ++k)
+        if (tx + k * 1024 < B.n_items) lds[rk[k]] = v[k];
     }
-#pragma unroll
-    for (int k = 0; k < KB; ++k)
-      if (threadIdx.x + k * 1024 < B.n_items) lds[rk[k]] = v[k];
-  }
-  __syncthreads();
-  if (single) {
-    double v = 0.0;
-    for (uint32_t j = threadIdx.x; j < B.n_items; j += 1024) v += lds[j];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    if (threadIdx.x == 0) n_big = 0;  // (its readers of the bucket before are behind the barrier that ends a bucket)
     __syncthreads();
-    if (threadIdx.x == 0) {
-      double tot = 0.0;
-      for (int k = 0; k < 16; ++k) tot += part[k];
-      if (B.flags & TRANS_SPLIT)
-        atomic_add_f64(T.counts + B.arc_lo, tot);
-      else
-        T.counts[B.arc_lo] = tot;
-    }
-    return;
-  }
-  // one thread per arc; arcs with more than 32 items are left to whole waves afterwards (fixed summation order
-  // either way).  (A thread's 16 arcs advancing together, one item of each per step -- 16 independent LDS reads per
-  // step instead of a chain per arc -- was measured 50 % slower on config 4, 86 -> 132 us: the loop is not what the
-  // kernel waits for, and the 48 extra registers cost more than the chains.)
-  if (threadIdx.x == 0) n_big = 0;
-  __syncthreads();
+    // The next descriptor is made scalar HERE: every load of this thread has arrived (their values are in LDS), so there is
+    // nothing to wait for -- and this bucket's stores are not issued yet.  Loads and stores count down one counter, which can
+    // only be waited for as a whole once both kinds are pending: behind the stores this would be a wait for all of them.
+    BucketAhead An = A;
+    if (WALK) An = bw_uniform(raw);
+    if (single) {
+      double v = 0.0;
+      for (uint32_t j = threadIdx.x; j < B.n_items; j += 1024) v += lds[j];
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+      if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int k = 0; k < 16; ++k) tot += part[k];
+        if (B.flags & TRANS_SPLIT)
+          atomic_add_f64(T.counts + B.arc_lo, tot);
+        else
+          T.counts[B.arc_lo] = tot;
+      }
+    } else {
+      // one thread per arc; arcs with more than 32 items are left to whole waves afterwards (fixed summation order
+      // either way).  (A thread's 16 arcs advancing together, one item of each per step -- 16 independent LDS reads per
+      // step instead of a chain per arc -- was measured 50 % slower on config 4, 86 -> 132 us: the loop is not what the
+      // kernel waits for, and the 48 extra registers cost more than the chains.)
 #pragma unroll
-  for (int k = 0; k < KB; ++k) {
-    const uint32_t a = threadIdx.x + k * 1024;
-    if (a >= B.n_arcs) break;
-    const uint32_t q0 = r0[k], q1 = a + 1 < B.n_arcs ? (uint32_t)r1[k] : B.n_items;
-    if (q1 - q0 > 32) {
-      const uint32_t q = atomicAdd(&n_big, 1u);
-      if (q < 512) {
-        big[q] = a;
-        continue;
+      for (int k = 0; k < KB; ++k) {
+        const uint32_t a = tx + k * 1024;
+        if (a < B.n_arcs) {
+          const uint32_t q0 = r01[k] & 0xffffu, q1 = a + 1 < B.n_arcs ? r01[k] >> 16 : B.n_items;
+          uint32_t q = 512u;  // (its place among the big arcs, if it is one of the first 512)
+          if (q1 - q0 > 32) q = atomicAdd(&n_big, 1u);
+          if (q < 512u)
+            big[q] = a;
+          else {
+            double v = 0.0;
+            for (uint32_t r = q0; r < q1; ++r) v += lds[r];
+            T.counts[B.arc_lo + a] = v;
+          }
+        }
+      }
+      __syncthreads();
+      const uint32_t nb = n_big < 512 ? n_big : 512;
+      for (uint32_t q = threadIdx.x >> 6; q < nb; q += 16) {
+        const uint32_t a = big[q];
+        const uint32_t q0 = T.a_off[B.arc_lo + a], q1 = a + 1 < B.n_arcs ? (uint32_t)T.a_off[B.arc_lo + a + 1] : B.n_items;
+        double v = 0.0;
+        for (uint32_t r = q0 + (threadIdx.x & 63); r < q1; r += 64) v += lds[r];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((threadIdx.x & 63) == 0) T.counts[B.arc_lo + a] = v;
       }
     }
-    double v = 0.0;
-    for (uint32_t r = q0; r < q1; ++r) v += lds[r];
-    T.counts[B.arc_lo + a] = v;
-  }
-  __syncthreads();
-  const uint32_t nb = n_big < 512 ? n_big : 512;
-  for (uint32_t q = threadIdx.x >> 6; q < nb; q += 16) {
-    const uint32_t a = big[q];
-    const uint32_t q0 = T.a_off[B.arc_lo + a], q1 = a + 1 < B.n_arcs ? (uint32_t)T.a_off[B.arc_lo + a + 1] : B.n_items;
-    double v = 0.0;
-    for (uint32_t r = q0 + (threadIdx.x & 63); r < q1; r += 64) v += lds[r];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) T.counts[B.arc_lo + a] = v;
+    if (!WALK || !nxt.ok) break;  // (uniform)
+    __syncthreads();  // everyone has read this bucket's items (and n_big, part) out of LDS before the next bucket's are written
+    A = An;
+    cur = nxt;
+    vidx += gridDim.x;
   }
 }
 __global__ void zero_list_kernel(double* p, const uint32_t* idx, uint32_t n) {
@@ -1669,6 +1807,10 @@ static void trans_lds_attr() {
   TRANS_SET_LDS((trans_c_bucket_kernel<false, false>), lds);
   TRANS_SET_LDS((trans_c_bucket_kernel<true, false>), lds_rl);
   TRANS_SET_LDS((trans_c_bucket_kernel<false, true>), lds);
+  // ... the count pass's walking forms (TransArgs::bucket_walk)
+  TRANS_SET_LDS((trans_c_bucket_kernel<false, false, TRANS_KB, true>), lds);
+  TRANS_SET_LDS((trans_c_bucket_kernel<true, false, TRANS_KB, true>), lds_rl);
+  TRANS_SET_LDS((trans_c_bucket_kernel<false, true, TRANS_KB, true>), lds);
   {  // the half-size bucket kernels (their static LDS takes them past the default limit as well)
     constexpr int KH = TRANS_KB / 2;
     TRANS_SET_LDS((trans_w_bucket_kernel<false, false, KH>), lds);
@@ -1679,6 +1821,30 @@ static void trans_lds_attr() {
     TRANS_SET_LDS((trans_c_bucket_kernel<false, true, KH>), lds);
   }
   __atomic_store_n(&done, (unsigned char)1, __ATOMIC_RELEASE);
+}
+// The walking form of the count pass over `count` buckets: its grid, or 0 for one workgroup per bucket.  A workgroup per CU
+// at most (a bucket's LDS is most of a CU's: one is resident), a multiple of 8 (XCDs) -- where the buckets are no more than
+// that there is nothing to walk and the launch stays one workgroup per bucket (bench.py's c2).  TransArgs::bucket_walk = N:
+// at most N workgroups, walking form whatever the bucket count.  The half-size buckets of the fused-lane layout, two
+// workgroups to a CU, keep their one workgroup per bucket.
+static uint32_t trans_walk_grid(const TransArgs& T, uint32_t count) {
+  if (!T.bucket_walk || T.bucket != TRANS_BUCKET) return 0;
+  uint32_t cap = T.bucket_walk;
+  if (cap == TRANS_WALK_AUTO) {
+    // per device, asked once (written once per device; racing writers store the same value)
+    static int dev_cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (!__atomic_load_n(&dev_cus[dev], __ATOMIC_ACQUIRE)) {
+      hipDeviceProp_t prop;
+      if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+      __atomic_store_n(&dev_cus[dev], prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8, __ATOMIC_RELEASE);
+    }
+    cap = (uint32_t)__atomic_load_n(&dev_cus[dev], __ATOMIC_ACQUIRE);
+    if (cap >= (count + 7) / 8 * 8) return 0;
+  } else
+    cap = cap > (1u << 20) ? (1u << 20) : (cap + 7) / 8 * 8;
+  return std::min(cap, (count + 7) / 8 * 8);
 }
 hipError_t launch_trans_w_bucket_range(const TransArgs& T0, uint32_t first, uint32_t count, hipStream_t stream) {
   trans_lds_attr();
@@ -1773,6 +1939,15 @@ hipError_t launch_trans_c_bucket_range(const TransArgs& T0, uint32_t first, uint
     return hipGetLastError();
   }
   if (T.bucket != TRANS_BUCKET) return hipErrorInvalidValue;
+  if (const uint32_t gw = trans_walk_grid(T, count)) {
+    if (T.scatter & 2u)
+      hipLaunchKernelGGL((trans_c_bucket_kernel<false, true, TRANS_KB, true>), dim3(gw), dim3(1024), TRANS_BUCKET * 8, stream, T);
+    else if (T.use_runs)
+      hipLaunchKernelGGL((trans_c_bucket_kernel<true, false, TRANS_KB, true>), dim3(gw), dim3(1024), TRANS_BUCKET * 8 + TRANS_RUN_LDS, stream, T);
+    else
+      hipLaunchKernelGGL((trans_c_bucket_kernel<false, false, TRANS_KB, true>), dim3(gw), dim3(1024), TRANS_BUCKET * 8, stream, T);
+    return hipGetLastError();
+  }
   if (T.scatter & 2u)
     hipLaunchKernelGGL((trans_c_bucket_kernel<false, true>), g8, dim3(1024), TRANS_BUCKET * 8, stream, T);
   else if (T.use_runs)

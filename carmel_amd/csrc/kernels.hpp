@@ -125,13 +125,19 @@ struct TransArgs {
   uint32_t bucket;          // items a bucket holds at most (LatticeSet::bucket: TRANS_BUCKET or half of it)
   uint32_t tile_first, tile_count;  // the tile range of this launch (a chunk of a lane class, or the bundle tiles)
   uint32_t bucket_first, bucket_count;  // the bucket range of this launch of a bucket pass (arc-range chunks of the exchange)
-  uint32_t slack_bytes;     // readable bytes behind x / xc / t_pos / t_src (DEVBUF_SLACK when they are DevBufs, engine.hpp): the
-                            // persistent tile kernels read whole rounds past a tile's last item
+  uint32_t slack_bytes;     // readable bytes behind x / xc / t_pos / t_src / a_off (DEVBUF_SLACK when they are DevBufs, engine.hpp):
+                            // the persistent tile kernels read whole rounds past a tile's last item, trans_c_bucket_kernel two
+                            // bytes past the last arc's a_off
   // tile_sweep_kernel, when asked: counts[zero_list[0 .. n_zero)] := 0 on its way in -- the arcs whose items lie in several
   // buckets, which the count pass adds up with atomics (instead of a zero_list_kernel launch between the sweep and the count pass)
   const uint32_t* zero_list = nullptr;
   uint32_t n_zero = 0;
+  // the count pass over the buckets (option trans_bucket_walk): 0 = one workgroup per bucket; N = at most N workgroups
+  // (rounded up to a multiple of 8), each walking the buckets of its XCD's eighth a grid apart with the next bucket's
+  // descriptor requested while this one is worked on; TRANS_WALK_AUTO = a workgroup per CU
+  uint32_t bucket_walk = 0xffffffffu;
 };
+#define TRANS_WALK_AUTO 0xffffffffu
 
 #define TRANS_RUN_CAP 4096
 #define TRANS_RUN_LDS (TRANS_RUN_CAP * 4 + 4096)  // r_src + the run-start mask and its prefix counts (RunLds, kernels.hip)
