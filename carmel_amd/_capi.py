@@ -18,7 +18,7 @@ SYMBOLS = [
     "carmel_hip_set_cascade", "carmel_hip_normalize", "carmel_hip_set_weights", "carmel_hip_get_weights",
     "carmel_hip_get_arc_weights", "carmel_hip_estimate", "carmel_hip_estimate_async",
     "carmel_hip_estimate_finish", "carmel_hip_counts_dev", "carmel_hip_counts_len", "carmel_hip_stream",
-    "carmel_hip_use_external_counts", "carmel_hip_synchronize", "carmel_hip_last_sweep_ms", "carmel_hip_read_scalars",
+    "carmel_hip_use_external_counts", "carmel_hip_synchronize", "carmel_hip_last_sweep_ms", "carmel_hip_weights_ahead_stats", "carmel_hip_read_scalars",
     "carmel_hip_get_counts", "carmel_hip_set_counts", "carmel_hip_maximize", "carmel_hip_keep_em_weights", "carmel_hip_random_restart", "carmel_hip_save_counts",
     "carmel_hip_fractional_counts", "carmel_hip_set_digamma",
     "carmel_hip_save_best", "carmel_hip_load_best", "carmel_hip_host_build", "carmel_hip_host_dims",
@@ -152,6 +152,7 @@ def _load():
     lib.carmel_hip_use_external_counts.argtypes = [vp, vp]
     lib.carmel_hip_synchronize.argtypes = [vp]
     lib.carmel_hip_last_sweep_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.carmel_hip_weights_ahead_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.carmel_hip_read_scalars.argtypes = [vp, C.POINTER(EstimateResult)]
     lib.carmel_hip_get_counts.argtypes = [vp, vp]
     lib.carmel_hip_set_counts.argtypes = [vp, vp]

@@ -81,7 +81,9 @@ int carmel_hip_create(carmel_hip_trainer** out, int device, uint32_t n_states, u
     delete t;
     return fail(CARMEL_HIP_ERR_HIP, hipGetErrorString(e));
   }
-  (void)hipEventCreate(&t->ev0);
+  (void)hipEventCreate(&t->ev_start[0]);
+  (void)hipEventCreate(&t->ev_start[1]);
+  t->ev0 = t->ev_start[0];
   (void)hipEventCreate(&t->ev1);
   (void)hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking);
   (void)hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming);
@@ -143,7 +145,8 @@ int carmel_hip_destroy(carmel_hip_trainer* t) {
   if (t->stream) (void)hipStreamSynchronize(t->stream);
   if (t->matrix) matrix_release(t->matrix);
   t->matrix = nullptr;
-  if (t->ev0) (void)hipEventDestroy(t->ev0);
+  for (hipEvent_t e : t->ev_start)
+    if (e) (void)hipEventDestroy(e);
   if (t->ev1) (void)hipEventDestroy(t->ev1);
   if (t->side) (void)hipStreamSynchronize(t->side);
   if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
@@ -199,6 +202,11 @@ int carmel_hip_build_lattices(carmel_hip_trainer* t, int prune, int host_threads
   if (!t->have_corpus) return fail(CARMEL_HIP_ERR_STATE, "set_corpus first");
   HIPCHK(hipSetDevice(t->device));
   if (t->xplan) exchange_drop(t);  // the plan follows the lattices' transposition tables: plan again after a rebuild
+  {  // (an early weight pass may still be writing the X, or reading the bucket tables, about to be freed)
+    int arc = weights_ahead_drop(t);
+    if (arc) return arc;
+  }
+  layout_changed(t);
   if (t->scalars_pending) {  // (the side stream may still be reading the arrays about to be rebuilt)
     (void)hipStreamSynchronize(t->side);
     t->scalars_pending = false;
@@ -767,6 +775,7 @@ int carmel_hip_set_cascade(carmel_hip_trainer* t, uint64_t n_params, const doubl
   // composed weights from the chains (cascade.update)
   HIPCHK(launch_chain_update(t->arc_logw.p, t->arc_group.p, t->chain_off.p, t->chain_param.p, t->param_logw_c.p,
                              t->w.n_arcs, s));
+  weights_changed(t);
   HIPCHK(hipStreamSynchronize(s));
   return CARMEL_HIP_OK;
 }
@@ -830,6 +839,7 @@ static int run_mstep(carmel_hip_trainer* t, int use_counts, int save_old) {
   MstepArgs M;
   int rc = mstep_args(t, use_counts, save_old, M);
   if (rc) return rc;
+  weights_changed(t);
   // the one-pass window M-step of a whole model runs in its batched form, which also delivers the result (one launch instead
   // of two); mstep_wide: "0" = mstep_window_kernel + mstep_max_final_kernel (A/B), N >= 8 = a grid of at most N workgroups
   // instead of what the device holds at once
@@ -854,6 +864,7 @@ int carmel_hip_normalize(carmel_hip_trainer* t) {
   if (t->cascade)
     HIPCHK(launch_chain_update(t->arc_logw.p, t->arc_group.p, t->chain_off.p, t->chain_param.p, t->param_logw_c.p,
                                t->w.n_arcs, t->stream));
+  weights_changed(t);
   HIPCHK(hipStreamSynchronize(t->stream));
   return CARMEL_HIP_OK;
 }
@@ -866,6 +877,7 @@ int carmel_hip_set_weights(carmel_hip_trainer* t, const double* logw) {
     if (xrc) return xrc;
   }
   HIPCHK(hipMemcpyAsync(t->params(), logw, t->np() * sizeof(double), hipMemcpyHostToDevice, t->stream));
+  weights_changed(t);
   if (t->cascade)
     HIPCHK(launch_chain_update(t->arc_logw.p, t->arc_group.p, t->chain_off.p, t->chain_param.p, t->param_logw_c.p,
                                t->w.n_arcs, t->stream));
@@ -941,6 +953,67 @@ void trans_args(carmel_hip_trainer* t, TransArgs& T) {
   // workgroup per bucket (A/B, bit-identical results); N: at most N workgroups
   T.bucket_walk = TRANS_WALK_AUTO;
   if (const char* e = lib_opt("trans_bucket_walk")) T.bucket_walk = (uint32_t)std::max(0, atoi(e));
+}
+
+// The next E-step's weight pass ahead of time (option weights_ahead, "0" = off).  carmel_hip_maximize ends when the host has read
+// the M-step's largest change out of the mailbox; only then does the caller come back with the next E-step, whose first kernel --
+// the weight pass from arc order into X -- found the queue empty: the device stood idle for a host round trip per iteration.
+// That kernel reads the weights and the static bucket tables and writes X, which nobody else touches between two sweeps, so
+// maximize enqueues it itself, behind the M-step kernel and before it starts waiting: the device goes straight on, and the host's
+// way back, the caller's loop and the launches of the sweep and the count pass lie under it.  In an EM loop every maximize but
+// the last is followed by an estimate on unchanged weights; whatever else happens in between says so (weights_changed /
+// layout_changed), and the E-step then runs its own weight pass behind the stale one on the same stream.
+void weights_changed(carmel_hip_trainer* t) { ++t->weight_version; }
+void layout_changed(carmel_hip_trainer* t) { ++t->lattice_epoch; }
+// before X or the bucket tables are freed or rebuilt: an early pass may be in flight on them
+int weights_ahead_drop(carmel_hip_trainer* t) {
+  if (t->ahead.pending && t->stream) HIPCHK(hipStreamSynchronize(t->stream));
+  t->ahead.pending = false;
+  return CARMEL_HIP_OK;
+}
+// the tiles fetch their weights from the table (t_t_arc, build_run_tables): nothing goes through X
+static bool tiles_gather_weights(const carmel_hip_trainer* t, const TransArgs& T) {
+  return t->use_transpose && t->t_t_arc.n && !T.use_runs && !(T.scatter & 1u);
+}
+// the E-step's first kernel is the bucket pass of the weights (nothing but gathering sweeps / tiles: no weight goes through X)
+static bool weight_pass_through_x(const carmel_hip_trainer* t, const TransArgs& T) {
+  return t->use_transpose && t->wcache.n && !tiles_gather_weights(t, T);
+}
+// everything trans_w_bucket_kernel's result depends on besides the weights themselves and the tables' contents
+static bool same_weight_pass(const TransArgs& a, const TransArgs& b) {
+  return a.x == b.x && a.logw == b.logw && a.buckets == b.buckets && a.n_buckets == b.n_buckets && a.bucket == b.bucket &&
+         a.scatter == b.scatter && a.use_runs == b.use_runs && a.b_arc == b.b_arc && a.b_rank == b.b_rank && a.b_src == b.b_src &&
+         a.br_off == b.br_off && a.br_rel == b.br_rel && a.br_src == b.br_src;
+}
+// behind the M-step kernel of a plain maximize (no cascade, no exchange plan, no over-relaxation), whose result is in the mailbox
+static int weights_ahead_enqueue(carmel_hip_trainer* t) {
+  t->ahead.pending = false;  // (one left by an earlier maximize is stale now: the M-step has just rewritten the weights)
+  if (lib_opt_off("weights_ahead")) return CARMEL_HIP_OK;
+  // without the mailbox the host gets the result by synchronising the stream: an early pass would only delay it
+  if (!t->h_box || lib_opt_off("mailbox")) return CARMEL_HIP_OK;
+  if (t->cascade || t->xplan || !t->have_lattices || t->matrix || t->unrolled) return CARMEL_HIP_OK;
+  TransArgs T;
+  trans_args(t, T);
+  if (!weight_pass_through_x(t, T) || !T.n_buckets) return CARMEL_HIP_OK;
+  // the opening time stamp of the E-step that will take this pass: not the event the last E-step's time is read from.  (From
+  // here to that E-step's closing stamp lie the weight pass, the sweep and the count pass and, were the host ever late with the
+  // sweep's launch, its lateness.)
+  const int start = 1 - t->ev0_idx;
+  HIPCHK(hipEventRecord(t->ev_start[start], t->stream));
+  HIPCHK(launch_trans_w_bucket(T, t->stream));
+  t->ahead.T = T;
+  t->ahead.start = start;
+  t->ahead.weight_version = t->weight_version;
+  t->ahead.layout_version = t->lattice_epoch;
+  t->ahead.pending = true;
+  ++t->ahead_enqueued;
+  return CARMEL_HIP_OK;
+}
+int carmel_hip_weights_ahead_stats(carmel_hip_trainer* t, uint64_t* enqueued, uint64_t* consumed) {
+  if (!t) return fail(CARMEL_HIP_ERR_ARG, "null trainer");
+  if (enqueued) *enqueued = t->ahead_enqueued;
+  if (consumed) *consumed = t->ahead_consumed;
+  return CARMEL_HIP_OK;
 }
 
 // CARMEL_HIP_POISON=2 (debugging): LDS keeps what the last workgroup on the CU left there -- zeros on an idle box, somebody's
@@ -1031,9 +1104,14 @@ static int estimate_enqueue(carmel_hip_trainer* t, bool timed) {
     int rc = scalars_join(t);
     if (rc) return rc;
   }
-  if (t->cascade)  // cascade.update(): composed weights from the chains
+  // an early weight pass (weights_ahead_enqueue) is this E-step's to take or to drop: none outlives an E-step
+  const carmel_hip_trainer::WeightsAhead ahead = t->ahead;
+  t->ahead.pending = false;
+  if (t->cascade) {  // cascade.update(): composed weights from the chains
     HIPCHK(launch_chain_update(t->arc_logw.p, t->arc_group.p, t->chain_off.p, t->chain_param.p, t->param_logw_c.p,
                                t->w.n_arcs, s));
+    weights_changed(t);
+  }
   if (t->matrix) {  // carmel --matrix-fb: no lattice is swept
     if (timed) HIPCHK(hipEventRecord(t->ev0, s));
     int rc = matrix_estimate(t, t->matrix, s);
@@ -1144,7 +1222,17 @@ static int estimate_enqueue(carmel_hip_trainer* t, bool timed) {
     T.n_post = t->post.n;
   }
   ExchangePlan* const xp = (t->xplan && exchange_is_sharded(t->xplan) && t->use_transpose) ? t->xplan : nullptr;
-  if (timed) HIPCHK(hipEventRecord(t->ev0, s));
+  // X already holds these weights in this layout if maximize sent the pass ahead and nothing has happened since: the E-step
+  // begins with that pass and its time stamp.  Otherwise it begins here, behind a stale pass if there is one (the same stream:
+  // what that wrote is overwritten).
+  const bool ahead_taken = !xp && ahead.pending && weight_pass_through_x(t, T) && ahead.weight_version == t->weight_version &&
+                           ahead.layout_version == t->lattice_epoch && same_weight_pass(ahead.T, T);
+  if (ahead_taken) {
+    t->ev0_idx = ahead.start;
+    t->ev0 = t->ev_start[t->ev0_idx];
+    ++t->ahead_consumed;
+  } else if (timed)
+    HIPCHK(hipEventRecord(t->ev0, s));
   const uint32_t lane_tiles = (uint32_t)((t->wcache.n + t->lat.tile - 1) / t->lat.tile);
   // a corpus of plain lane lattices laid out for it: weights in, sweeps and posteriors out of a tile in one kernel
   // (CARMEL_HIP_TILE_SWEEP_KERNEL=0: the three kernels on the same layout, bit-identical)
@@ -1155,7 +1243,7 @@ static int estimate_enqueue(carmel_hip_trainer* t, bool timed) {
   // the tile sweep clears, on its way in, the counts the count pass adds up with atomics (the arcs whose items lie in several
   // buckets): one launch less between the sweep and the count pass (the exchange clears its own, chunk by chunk)
   // the tiles' weights straight from the table (t_t_arc, build_run_tables): the tile kernels read `x[t_src[i]]`, whatever the two are
-  const bool tile_gather = t->use_transpose && t->t_t_arc.n && !T.use_runs && !(T.scatter & 1u);
+  const bool tile_gather = tiles_gather_weights(t, T);
   TransArgs TW = T;
   if (tile_gather) {
     TW.x = const_cast<double*>(T.logw);
@@ -1172,7 +1260,7 @@ static int estimate_enqueue(carmel_hip_trainer* t, bool timed) {
   if (xp) {  // the weights arrive arc range by arc range (all-gather of the sharded M-step): exchange.cpp
     int rc = exchange_weights_in(t, xp, T, t->wcache.n && !tile_gather);
     if (rc) return rc;
-  } else if (t->use_transpose && t->wcache.n && !tile_gather)  // (nothing but gathering sweeps / tiles: no weight goes through X)
+  } else if (weight_pass_through_x(t, T) && !ahead_taken)
     HIPCHK(launch_trans_w_bucket(T, s));
   if (bundles_beside) {  // (after the bucket pass: its workgroups need a CU's LDS nearly whole)
     HIPCHK(hipEventRecord(t->ev_b0, s));
@@ -1347,11 +1435,13 @@ int carmel_hip_estimate_async(carmel_hip_trainer* t) {
 int carmel_hip_set_layout_policy(carmel_hip_trainer* t, int allow_unrolled) {
   if (!t) return fail(CARMEL_HIP_ERR_ARG, "null trainer");
   t->allow_unrolled = allow_unrolled != 0;
+  layout_changed(t);
   return CARMEL_HIP_OK;
 }
 int carmel_hip_set_matrix_fb(carmel_hip_trainer* t, int on) {
   if (!t) return fail(CARMEL_HIP_ERR_ARG, "null trainer");
   HIPCHK(hipSetDevice(t->device));
+  layout_changed(t);
   if (t->matrix) {
     HIPCHK(hipStreamSynchronize(t->stream));
     matrix_release(t->matrix);
@@ -1415,7 +1505,7 @@ int carmel_hip_estimate_finish(carmel_hip_trainer* t, carmel_hip_estimate_result
   int rc = carmel_hip_read_scalars(t, &r);
   if (rc) return rc;
   float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+  HIPCHK(hipEventElapsedTime(&ms, t->ev0, t->ev1));  // (ev0: in front of the weight pass, wherever that was enqueued)
   r.kernel_ms = ms;
   if (per_pair_logprob) {
     HIPCHK(hipMemcpyAsync(per_pair_logprob, t->pair_logprob.p, t->corpus.n_pairs * sizeof(double),
@@ -1449,7 +1539,7 @@ int carmel_hip_last_sweep_ms(carmel_hip_trainer* t, double* ms) {
   HIPCHK(hipSetDevice(t->device));
   HIPCHK(hipEventSynchronize(t->ev1));
   float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, t->ev0, t->ev1));
+  HIPCHK(hipEventElapsedTime(&f, t->ev0, t->ev1));  // (ev0: in front of the weight pass, wherever that was enqueued)
   *ms = f;
   return CARMEL_HIP_OK;
 }
@@ -1534,6 +1624,7 @@ int carmel_hip_accumulate_counts(carmel_hip_trainer* t, int op) {
     return fail(CARMEL_HIP_ERR_STATE, "carmel_hip_accumulate_counts: explicit lattices only (carmel_hip_set_layout_policy(t, 0) before build_lattices)");
   const uint64_t n = t->w.n_arcs + 4;
   hipStream_t s = t->stream;
+  layout_changed(t);  // (a corpus walked shard by shard: the lattices in place at the next E-step need not be these)
   {
     int jrc = scalars_join(t);
     if (jrc) return jrc;
@@ -1587,6 +1678,7 @@ int carmel_hip_maximize(carmel_hip_trainer* t, double delta_scale, double* max_c
   if (!t->cascade) {
     if (delta_scale > 1.0) {
       HIPCHK(launch_overrelax(t->arc_logw.p, t->old_logw.p, t->em_logw.p, t->arc_group.p, delta_scale, t->w.n_arcs, s));
+      weights_changed(t);
       rc = run_mstep(t, 0, 0);  // x.normalize(methods[0]) on the overrelaxed weights, scratch kept
       if (rc) return rc;
       HIPCHK(hipMemsetAsync(t->maxchg.p, 0, sizeof(unsigned long long), s));
@@ -1594,6 +1686,10 @@ int carmel_hip_maximize(carmel_hip_trainer* t, double delta_scale, double* max_c
       t->em_valid = true;
     } else {
       t->em_valid = false;  // the EM update IS the weight vector: nothing to keep apart (train.cc:157-171 only acts for rate > 1)
+      // the next E-step's weight pass goes out now, before the host starts waiting at the mailbox (not under an exchange plan,
+      // whose weights arrive arc range by arc range: weights_ahead_enqueue)
+      rc = weights_ahead_enqueue(t);
+      if (rc) return rc;
     }
     unsigned long long bits = 0;
     int frc = fetch_u64(t, t->maxchg.p, &bits, s, !(delta_scale > 1.0));  // (an over-relaxed step ends in max_change_kernel)
@@ -1639,6 +1735,7 @@ int carmel_hip_fractional_counts(carmel_hip_trainer* t) {
     HIPCHK(launch_counts_to_logw(t->arc_logw.p, t->counts_ptr(), (t->have_prior && t->prior_nonzero) ? t->prior.p : nullptr,
                                  t->arc_group.p, t->w.n_arcs, s));
   }
+  weights_changed(t);
   HIPCHK(hipStreamSynchronize(s));
   return CARMEL_HIP_OK;
 }
@@ -1713,6 +1810,7 @@ int carmel_hip_keep_em_weights(carmel_hip_trainer* t) {
     if (xrc) return xrc;
   }
   HIPCHK(hipMemcpyAsync(t->arc_logw.p, t->em_logw.p, t->w.n_arcs * sizeof(double), hipMemcpyDeviceToDevice, t->stream));
+  weights_changed(t);
   HIPCHK(hipStreamSynchronize(t->stream));
   return CARMEL_HIP_OK;
 }
@@ -1759,6 +1857,7 @@ int carmel_hip_load_best(carmel_hip_trainer* t) {
   hipStream_t s = t->stream;
   if (!t->cascade) {
     HIPCHK(hipMemcpyAsync(t->arc_logw.p, t->best_logw.p, t->w.n_arcs * sizeof(double), hipMemcpyDeviceToDevice, s));
+    weights_changed(t);
     HIPCHK(hipStreamSynchronize(s));
     return CARMEL_HIP_OK;
   }
@@ -1779,6 +1878,7 @@ int carmel_hip_load_best(carmel_hip_trainer* t) {
   if (rc) return rc;
   HIPCHK(launch_chain_update(t->arc_logw.p, t->arc_group.p, t->chain_off.p, t->chain_param.p, t->param_logw_c.p,
                              t->w.n_arcs, s));
+  weights_changed(t);
   HIPCHK(hipStreamSynchronize(s));
   return CARMEL_HIP_OK;
 }

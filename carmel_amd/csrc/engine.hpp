@@ -182,7 +182,25 @@ struct carmel_hip_trainer {
   DevBuf<uint8_t> d_a_has, d_b_has;
   DevBuf<uint16_t> d_Bslot, d_sym;
   DevBuf<uint64_t> d_sym_off, d_vbuf_off;
-  // the E-step as a replayed hipGraph (engine.cpp: carmel_hip_estimate_async)
+  // the next E-step's weight pass, enqueued by carmel_hip_maximize behind the M-step kernel (option weights_ahead; engine.cpp:
+  // weights_ahead_enqueue, estimate_enqueue).  weight_version counts what has written the weights (weights_changed),
+  // lattice_epoch what has rebuilt or re-pointed the lattices and their bucket tables (layout_changed); the next E-step skips
+  // its own weight pass only if both still stand where the early pass found them and the pass ran on the arguments the E-step
+  // would use now.  An early pass lives until the next E-step, which takes it or drops it.
+  struct WeightsAhead {
+    bool pending = false;
+    uint64_t weight_version = 0, layout_version = 0;  // the trainer's weight_version / lattice_epoch when it was enqueued
+    TransArgs T;      // the fields that decide X's contents and layout are compared one by one (same_weight_pass)
+    int start = 0;    // which of ev_start was recorded in front of it
+  } ahead;
+  uint64_t weight_version = 0;
+  uint64_t ahead_enqueued = 0, ahead_consumed = 0;  // carmel_hip_weights_ahead_stats
+  // the E-step's opening time stamp is one of two events used in turn (ev0 is the last E-step's): an early pass is stamped in
+  // front with the OTHER one, so carmel_hip_last_sweep_ms, asked about an E-step after the maximize behind it has sent the next
+  // pass ahead, still finds that E-step's pair; the E-step that takes the pass takes the stamp with it and records none itself
+  // (every event record between two kernels is a bubble of 5-6 us: profiles/measurement_log_weights_ahead.md)
+  hipEvent_t ev_start[2] = {nullptr, nullptr};
+  int ev0_idx = 0;  // ev0 == ev_start[ev0_idx]
   uint64_t lattice_epoch = 0;
   bool use_transpose = false;
   bool em_valid = false;  // em_logw holds the plain EM update of the last (over-relaxed) maximize
@@ -220,6 +238,12 @@ bool exchange_is_sharded(const ExchangePlan* xp);  // exchange.cpp
 // s was an M-step's mstep_max_final_kernel, which has already stored it)
 extern "C" int publish_u64(carmel_hip_trainer* t, const unsigned long long* dev, hipStream_t s);
 extern "C" int fetch_u64(carmel_hip_trainer* t, const unsigned long long* dev, unsigned long long* out, hipStream_t s, bool published);
+// engine.cpp, the early weight pass: whoever writes the weights (arc_logw / params()) calls weights_changed, whoever rebuilds
+// the lattices or changes which tables the E-step reads layout_changed; weights_ahead_drop waits for a pass in flight before
+// X or the bucket tables are freed
+extern "C" void weights_changed(carmel_hip_trainer* t);
+extern "C" void layout_changed(carmel_hip_trainer* t);
+extern "C" int weights_ahead_drop(carmel_hip_trainer* t);
 extern "C" int scalars_join(carmel_hip_trainer* t);  // engine.cpp: before anything reads counts[n_arcs .. n_arcs + 4) on the trainer's stream
 namespace carmel_hip {  // matrix_fb.hip
 int matrix_setup(carmel_hip_trainer* t, void** out);

@@ -120,6 +120,7 @@ void exchange_drop(carmel_hip_trainer* t) {
   if (t->stream) (void)hipStreamSynchronize(t->stream);
   plan_free(t->xplan);
   t->xplan = nullptr;
+  layout_changed(t);  // (the next E-step takes its weights in one pass again)
 }
 
 void exchange_comm_gone(carmel_hip_comm* c) {
@@ -441,6 +442,7 @@ int exchange_maximize(carmel_hip_trainer* t, ExchangePlan* xp, double* max_chang
     }
   }
   HIPCHK(hipEventRecord(xp->ev_ag_done, x));
+  weights_changed(t);  // (this rank's M-step and the gathers of everybody else's)
   xp->ag_pending = true;
   xp->counts_sharded = false;  // consumed
   t->em_valid = false;
@@ -760,6 +762,7 @@ int carmel_hip_exchange_plan(carmel_hip_trainer* t, carmel_hip_comm* c, uint32_t
   }
   t->xplan = xp;
   c->planned.push_back(t);
+  layout_changed(t);  // (an early weight pass of the unplanned trainer is not this plan's: exchange_weights_in sends its own)
   return CARMEL_HIP_OK;
 }
 
@@ -840,6 +843,7 @@ int carmel_hip_exchange_measure(carmel_hip_trainer* t, uint32_t reps, double* ms
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(t->counts_ptr(), keep_c.p, n * 8, hipMemcpyDeviceToDevice, x));
   HIPCHK(hipMemcpyAsync(t->arc_logw.p, keep_w.p, t->w.n_arcs * 8, hipMemcpyDeviceToDevice, x));
+  weights_changed(t);  // (the gathers above wrote them, this restores them)
   HIPCHK(hipStreamSynchronize(x));
   *ms_per_exchange = total / reps;
   return CARMEL_HIP_OK;

@@ -238,6 +238,12 @@ class HipForwardBackward(object):
         check(lib.carmel_hip_last_sweep_ms(self.h, C.byref(ms)), "carmel_hip_last_sweep_ms")
         return ms.value
 
+    def weights_ahead_stats(self):
+        """(enqueued, consumed): early weight passes maximize() has sent ahead, and those the next estimate took in place of its own"""
+        enq, con = C.c_uint64(0), C.c_uint64(0)
+        check(lib.carmel_hip_weights_ahead_stats(self.h, C.byref(enq), C.byref(con)), "carmel_hip_weights_ahead_stats")
+        return enq.value, con.value
+
     def read_scalars(self):
         res = EstimateResult()
         check(lib.carmel_hip_read_scalars(self.h, C.byref(res)), "carmel_hip_read_scalars")

@@ -179,8 +179,14 @@ void* carmel_hip_stream(carmel_hip_trainer* t); /* hipStream_t the trainer enque
  * n_arcs + 4 doubles on this trainer's device and outlive the trainer; NULL switches back. */
 int carmel_hip_use_external_counts(carmel_hip_trainer* t, void* dev_ptr);
 int carmel_hip_synchronize(carmel_hip_trainer* t); /* wait for everything enqueued on the trainer's stream */
-/* HIP-event time (ms) of the sweep kernels of the most recent estimate, measured on the trainer's stream */
+/* HIP-event time (ms) of the sweep kernels of the most recent estimate, measured on the trainer's stream (from in front of its
+ * weight pass, which carmel_hip_maximize may have sent ahead, to behind its count pass) */
 int carmel_hip_last_sweep_ms(carmel_hip_trainer* t, double* ms);
+/* The next E-step's weight pass ahead of time (option weights_ahead, "0" = off): a plain carmel_hip_maximize (delta_scale <= 1, no
+ * cascade, no exchange plan, the mailbox in use) enqueues it behind its M-step kernel, and the next carmel_hip_estimate takes it
+ * in place of its own if neither the weights nor the lattices have been touched in between.  enqueued / consumed count both
+ * events since carmel_hip_create (either pointer may be NULL); results are the same bits either way. */
+int carmel_hip_weights_ahead_stats(carmel_hip_trainer* t, uint64_t* enqueued, uint64_t* consumed);
 /* after an external all-reduce of counts_dev: re-read the three scalars into res */
 int carmel_hip_read_scalars(carmel_hip_trainer* t, carmel_hip_estimate_result* res);
 int carmel_hip_get_counts(carmel_hip_trainer* t, double* counts /* n_arcs, linear */);
