@@ -3,17 +3,10 @@
 // weights.  The reference composes each line with the machine and runs a reversed Dijkstra over the result (kbest.h:189,
 // graph.cc:148-208); here nothing is composed per line: a line only selects which arcs may advance a position.
 //
-// Line-independent preparation (carmel_hip_decoder_create, on the host, uploaded once):
-//   * the matched arcs (the matched side -- input, or output for side 1 -- is not *e*) in a CSR by symbol, each symbol's arcs
-//     sorted by (dst, arc id) and cut into one segment per destination state;
-//   * the epsilon arcs (matched side *e*) grouped into levels: level(q) = 1 + the largest level of an epsilon predecessor of q
-//     (0 without one), an arc filed under the level of its destination.  If the epsilon subgraph has a cycle there are no
-//     levels: the closure relaxes every epsilon arc in arc-id order, round after round, to a fixed point (at most |Q| rounds).
-//   Arcs of weight zero are dropped here: they are never taken.
-//   * for the pair decoder (decode_pairs.hip, DecodePairTables): the other side's symbol of every arc, and the epsilon arcs by the
-//     levels of the subgraph of the arcs with epsilon on BOTH sides, which exist also when the levels above do not;
-//   * the same arcs filed under their SOURCES (DecodeOutTables, for the backward pass of decode_posterior.hip): matched arcs by
-//     (symbol, src, arc id), one segment per source; epsilon arcs by (level of src, src, arc id), one entry per source.
+// Line-independent preparation (carmel_hip_decoder_create, and again on carmel_hip_decoder_set_weights): the host builds the
+// tables of decode_tables.hpp -- the matched arcs in a CSR by symbol, the epsilon arcs by levels, each by destination and by
+// source, and the epsilon arcs once more by the levels of the 00 subgraph for the pair decoders -- and upload_tables below copies
+// every one of them to the device as it is.  Arcs of weight zero are dropped there: they are never taken.
 //
 // Per line (one wavefront = one workgroup of 64 lanes per line; lines launched longest first):
 //   d_0 = 0 at the start state (0), -inf elsewhere, closed over the epsilon arcs;
@@ -38,7 +31,6 @@
 // The tables, the handle, the constants and the host drivers are in decode.hpp, shared with the k-best decoder
 // (decode_kbest.hip) and the all-paths sum (decode_sum.hip); this kernel alone closes a cyclic epsilon subgraph.
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -156,294 +148,43 @@ void carmel_hip::launch_decode_trellis(const carmel_hip_decoder* d, bool lds, ui
 }
 
 int carmel_hip_decoder::upload_tables() {
-  const double ninf = -std::numeric_limits<double>::infinity();
-  const uint32_t Q = n_states;
-  std::vector<uint32_t> matched, eps;
-  uint32_t n_syms = 0;
-  for (uint64_t k = 0; k < n_arcs; ++k) {
-    if (!(logw[k] > ninf)) continue;  // zero-probability arcs are never taken
-    if (msym[k] == 0)
-      eps.push_back((uint32_t)k);
-    else {
-      matched.push_back((uint32_t)k);
-      n_syms = std::max(n_syms, msym[k] + 1);
-    }
-  }
-  // matched arcs: CSR by symbol, (symbol, dst, arc id) order, one segment per (symbol, dst)
-  std::stable_sort(matched.begin(), matched.end(), [&](uint32_t a, uint32_t b) {
-    return msym[a] != msym[b] ? msym[a] < msym[b] : dst[a] < dst[b];
-  });
-  std::vector<uint32_t> h_sym_seg(n_syms + 1, 0), h_seg_dst, h_seg_arc, h_msrc, h_mid;
-  std::vector<double> h_mw;
-  for (size_t j = 0; j < matched.size(); ++j) {
-    const uint32_t k = matched[j];
-    if (j == 0 || msym[k] != msym[matched[j - 1]] || dst[k] != dst[matched[j - 1]]) {
-      h_seg_dst.push_back(dst[k]);
-      h_seg_arc.push_back((uint32_t)j);
-      h_sym_seg[msym[k] + 1]++;
-    }
-    h_msrc.push_back(src[k]);
-    h_mw.push_back(logw[k]);
-    h_mid.push_back(k);
-  }
-  h_seg_arc.push_back((uint32_t)matched.size());
-  for (uint32_t x = 0; x < n_syms; ++x) h_sym_seg[x + 1] += h_sym_seg[x];
-  // epsilon arcs: levels of a topological order (Kahn), or one list in arc-id order if the subgraph is cyclic
-  std::vector<uint32_t> level(Q, 0), indeg(Q, 0);
-  std::vector<std::vector<uint32_t> > outs(Q);
-  for (uint32_t k : eps) {
-    outs[src[k]].push_back(k);
-    indeg[dst[k]]++;
-  }
-  std::vector<uint32_t> work;
-  for (uint32_t q = 0; q < Q; ++q)
-    if (!indeg[q]) work.push_back(q);
-  size_t seen = 0;
-  uint32_t n_levels = 0;
-  while (seen < work.size()) {
-    const uint32_t q = work[seen++];
-    for (uint32_t k : outs[q]) {
-      level[dst[k]] = std::max(level[dst[k]], level[q] + 1);
-      n_levels = std::max(n_levels, level[dst[k]]);
-      if (--indeg[dst[k]] == 0) work.push_back(dst[k]);
-    }
-  }
-  eps_cyclic = seen < Q;
-  std::vector<uint32_t> h_lvl_ent, h_ent_dst, h_ent_arc, h_esrc, h_edst, h_eid;
-  std::vector<double> h_ew;
-  if (eps_cyclic)
-    n_levels = 0;  // eps stays in arc-id order
-  else {
-    std::stable_sort(eps.begin(), eps.end(), [&](uint32_t a, uint32_t b) {
-      return level[dst[a]] != level[dst[b]] ? level[dst[a]] < level[dst[b]] : dst[a] < dst[b];
-    });
-    // levels 1 .. n_levels hold arcs (level 0 states have no epsilon predecessor)
-    h_lvl_ent.assign(n_levels + 1, 0);
-    for (size_t j = 0; j < eps.size(); ++j) {
-      const uint32_t k = eps[j];
-      if (j == 0 || dst[k] != dst[eps[j - 1]]) {
-        h_ent_dst.push_back(dst[k]);
-        h_ent_arc.push_back((uint32_t)j);
-        h_lvl_ent[level[dst[k]]]++;  // (level >= 1: counted into slot level - 1 + 1)
-      }
-    }
-    h_ent_arc.push_back((uint32_t)eps.size());
-    for (uint32_t L = 0; L < n_levels; ++L) h_lvl_ent[L + 1] += h_lvl_ent[L];
-  }
-  std::vector<uint32_t> h_stent(Q, kNone);  // the sampler's walk finds a state's epsilon arcs through its entry
-  for (size_t e = 0; e < h_ent_dst.size(); ++e) h_stent[h_ent_dst[e]] = (uint32_t)e;
-  for (uint32_t k : eps) {
-    h_esrc.push_back(src[k]);
-    h_edst.push_back(dst[k]);
-    h_ew.push_back(logw[k]);
-    h_eid.push_back(k);
-  }
-  std::vector<uint8_t> h_aeps(n_arcs);
-  for (uint64_t k = 0; k < n_arcs; ++k) h_aeps[k] = msym[k] == 0;
-  std::vector<uint8_t> h_epsin(Q, 0);
-  for (uint32_t k : eps) h_epsin[dst[k]] = 1;
-  // the outgoing view (DecodeOutTables): matched arcs by (symbol, src, arc id), one segment per (symbol, src); epsilon arcs by
-  // (level of src, src, arc id), one entry per source -- the same arcs, the same levels
-  std::vector<uint32_t> omatched(matched), oeps;
-  std::sort(omatched.begin(), omatched.end(), [&](uint32_t a, uint32_t b) {
-    return msym[a] != msym[b] ? msym[a] < msym[b] : src[a] != src[b] ? src[a] < src[b] : a < b;
-  });
-  std::vector<uint32_t> h_osym_seg(n_syms + 1, 0), h_oseg_src, h_oseg_arc, h_omdst, h_omid;
-  std::vector<double> h_omw;
-  for (size_t j = 0; j < omatched.size(); ++j) {
-    const uint32_t k = omatched[j];
-    if (j == 0 || msym[k] != msym[omatched[j - 1]] || src[k] != src[omatched[j - 1]]) {
-      h_oseg_src.push_back(src[k]);
-      h_oseg_arc.push_back((uint32_t)j);
-      h_osym_seg[msym[k] + 1]++;
-    }
-    h_omdst.push_back(dst[k]);
-    h_omw.push_back(logw[k]);
-    h_omid.push_back(k);
-  }
-  h_oseg_arc.push_back((uint32_t)omatched.size());
-  for (uint32_t x = 0; x < n_syms; ++x) h_osym_seg[x + 1] += h_osym_seg[x];
-  std::vector<uint32_t> h_olvl_ent(n_levels + 1, 0), h_oent_src, h_oent_arc, h_oedst, h_oeid, h_ostent(Q, kNone);
-  std::vector<double> h_oew;
-  std::vector<uint8_t> h_epsout(Q, 0);
-  if (!eps_cyclic) {
-    oeps = eps;
-    std::sort(oeps.begin(), oeps.end(), [&](uint32_t a, uint32_t b) {
-      return level[src[a]] != level[src[b]] ? level[src[a]] < level[src[b]] : src[a] != src[b] ? src[a] < src[b] : a < b;
-    });
-  }
-  for (size_t j = 0; j < oeps.size(); ++j) {
-    const uint32_t k = oeps[j];
-    if (j == 0 || src[k] != src[oeps[j - 1]]) {
-      h_ostent[src[k]] = (uint32_t)h_oent_src.size();
-      h_oent_src.push_back(src[k]);
-      h_oent_arc.push_back((uint32_t)j);
-      h_olvl_ent[level[src[k]] + 1]++;  // (a source's level is below its destinations': at most n_levels - 1)
-    }
-    h_oedst.push_back(dst[k]);
-    h_oew.push_back(logw[k]);
-    h_oeid.push_back(k);
-    h_epsout[src[k]] = 1;
-  }
-  h_oent_arc.push_back((uint32_t)oeps.size());
-  for (uint32_t L = 0; L < n_levels; ++L) h_olvl_ent[L + 1] += h_olvl_ent[L];
-  // the pair decoder's tables (DecodePairTables): the other side's symbols, and the epsilon arcs by the levels of the 00 subgraph
-  // alone (Kahn again, over the arcs with epsilon on both sides); from the epsilon arcs in arc-id order, never from the levels above
-  std::vector<uint32_t> h_mosym, peps, plevel(Q, 0), pindeg(Q, 0), h_plvl_ent, h_pent_dst, h_pent_arc, h_pesrc, h_peid, h_peosym;
-  std::vector<double> h_pew;
-  for (uint32_t k : matched) h_mosym.push_back(osym[k]);
-  uint32_t max_seg = 0;
-  for (uint32_t x = 0; x < n_syms; ++x) max_seg = std::max(max_seg, h_sym_seg[x + 1] - h_sym_seg[x]);
-  for (uint64_t k = 0; k < n_arcs; ++k)
-    if (logw[k] > ninf && msym[k] == 0) peps.push_back((uint32_t)k);
-  std::vector<std::vector<uint32_t> > pouts(Q);
-  for (uint32_t k : peps)
-    if (osym[k] == 0) {
-      pouts[src[k]].push_back(k);
-      pindeg[dst[k]]++;
-    }
-  work.clear();
-  for (uint32_t q = 0; q < Q; ++q)
-    if (!pindeg[q]) work.push_back(q);
-  pair_levels = 0;
-  for (seen = 0; seen < work.size();) {
-    const uint32_t q = work[seen++];
-    for (uint32_t k : pouts[q]) {
-      plevel[dst[k]] = std::max(plevel[dst[k]], plevel[q] + 1);
-      pair_levels = std::max(pair_levels, plevel[dst[k]]);
-      if (--pindeg[dst[k]] == 0) work.push_back(dst[k]);
-    }
-  }
-  pair_cycle.clear();
-  if (seen < Q) {  // name one cycle: from a state Kahn left, step to a predecessor it left too until a state repeats
-    std::vector<uint32_t> pred(Q, kNone), mark(Q, kNone);
-    for (uint32_t k : peps)
-      if (osym[k] == 0 && pindeg[src[k]] && pindeg[dst[k]] && pred[dst[k]] == kNone) pred[dst[k]] = src[k];
-    uint32_t q = 0;
-    while (!pindeg[q]) ++q;
-    uint32_t step = 0;
-    for (; mark[q] == kNone; q = pred[q]) mark[q] = step++;
-    std::string names = std::to_string(q);
-    for (uint32_t r = pred[q]; r != q; r = pred[r]) names = std::to_string(r) + " -> " + names;
-    pair_cycle = "states " + std::to_string(q) + " -> " + names;
-    pair_levels = 0;
-  } else {
-    std::stable_sort(peps.begin(), peps.end(), [&](uint32_t a, uint32_t b) {
-      return plevel[dst[a]] != plevel[dst[b]] ? plevel[dst[a]] < plevel[dst[b]] : dst[a] < dst[b];
-    });
-    h_plvl_ent.assign(peps.empty() ? 1 : pair_levels + 2, 0);
-    for (size_t j = 0; j < peps.size(); ++j) {
-      const uint32_t k = peps[j];
-      if (j == 0 || dst[k] != dst[peps[j - 1]]) {
-        h_pent_dst.push_back(dst[k]);
-        h_pent_arc.push_back((uint32_t)j);
-        h_plvl_ent[plevel[dst[k]] + 1]++;
-      }
-      h_pesrc.push_back(src[k]);
-      h_pew.push_back(logw[k]);
-      h_peid.push_back(k);
-      h_peosym.push_back(osym[k]);
-    }
-    h_pent_arc.push_back((uint32_t)peps.size());
-    for (size_t L = 0; L + 1 < h_plvl_ent.size(); ++L) h_plvl_ent[L + 1] += h_plvl_ent[L];
-  }
-  if (h_plvl_ent.empty()) h_plvl_ent.assign(1, 0);
-  std::vector<uint32_t> h_pstent(Q, kNone);  // the pair sampler's walk finds a state's matched-side-epsilon arcs through its entry
-  for (size_t e = 0; e < h_pent_dst.size(); ++e) h_pstent[h_pent_dst[e]] = (uint32_t)e;
-  // their outgoing view (DecodePairOutTables): the other side's symbols beside the outgoing matched CSR above, and the same
-  // epsilon arcs by (00 level of the source, source, arc id), one entry per source; nothing if the 00 arcs have a cycle
-  std::vector<uint32_t> h_omosym, poeps, h_polvl_ent(1, 0), h_poent_src, h_poent_arc, h_poedst, h_poeid, h_poeosym;
-  std::vector<double> h_poew;
-  std::vector<uint8_t> h_poepsout(Q, 0);
-  for (uint32_t k : omatched) h_omosym.push_back(osym[k]);
-  uint32_t max_oseg = 0;
-  for (uint32_t x = 0; x < n_syms; ++x) max_oseg = std::max(max_oseg, h_osym_seg[x + 1] - h_osym_seg[x]);
-  if (pair_cycle.empty() && !peps.empty()) {
-    poeps = peps;
-    std::sort(poeps.begin(), poeps.end(), [&](uint32_t a, uint32_t b) {
-      return plevel[src[a]] != plevel[src[b]] ? plevel[src[a]] < plevel[src[b]] : src[a] != src[b] ? src[a] < src[b] : a < b;
-    });
-    h_polvl_ent.assign(pair_levels + 2, 0);
-    for (size_t j = 0; j < poeps.size(); ++j) {
-      const uint32_t k = poeps[j];
-      if (j == 0 || src[k] != src[poeps[j - 1]]) {
-        h_poent_src.push_back(src[k]);
-        h_poent_arc.push_back((uint32_t)j);
-        h_polvl_ent[plevel[src[k]] + 1]++;
-      }
-      h_poedst.push_back(dst[k]);
-      h_poew.push_back(logw[k]);
-      h_poeid.push_back(k);
-      h_poeosym.push_back(osym[k]);
-      h_poepsout[src[k]] = 1;
-    }
-    for (size_t L = 0; L + 1 < h_polvl_ent.size(); ++L) h_polvl_ent[L + 1] += h_polvl_ent[L];
-  }
-  h_poent_arc.push_back((uint32_t)poeps.size());
-  std::vector<uint8_t> h_aflags(n_arcs);
-  for (uint64_t k = 0; k < n_arcs; ++k) h_aflags[k] = (msym[k] != 0 ? 1 : 0) | (osym[k] != 0 ? 2 : 0);
+  const DecodeTablesHost H = build_decode_tables(n_states, src, dst, msym, osym, logw);  // (lives until the copies have been made)
+  eps_cyclic = H.eps_cyclic;
+  pair_levels = H.pair_levels;
+  pair_cycle = H.pair_cycle;
+  tab_u32.clear();
+  tab_f64.clear();
+  tab_u8.clear();
   hipStream_t s = stream;
-  HIPCHK(p_m_osym.upload(h_mosym, s));
-  HIPCHK(p_lvl_ent.upload(h_plvl_ent, s));
-  HIPCHK(p_ent_dst.upload(h_pent_dst, s));
-  HIPCHK(p_ent_arc.upload(h_pent_arc, s));
-  HIPCHK(p_e_src.upload(h_pesrc, s));
-  HIPCHK(p_e_w.upload(h_pew, s));
-  HIPCHK(p_e_id.upload(h_peid, s));
-  HIPCHK(p_e_osym.upload(h_peosym, s));
-  HIPCHK(p_st_ent.upload(h_pstent, s));
-  HIPCHK(a_flags.upload(h_aflags, s));
-  HIPCHK(po_m_osym.upload(h_omosym, s));
-  HIPCHK(po_lvl_ent.upload(h_polvl_ent, s));
-  HIPCHK(po_ent_src.upload(h_poent_src, s));
-  HIPCHK(po_ent_arc.upload(h_poent_arc, s));
-  HIPCHK(po_e_dst.upload(h_poedst, s));
-  HIPCHK(po_e_w.upload(h_poew, s));
-  HIPCHK(po_e_id.upload(h_poeid, s));
-  HIPCHK(po_e_osym.upload(h_poeosym, s));
-  HIPCHK(po_eps_out.upload(h_poepsout, s));
-  HIPCHK(sym_seg.upload(h_sym_seg, s));
-  HIPCHK(seg_dst.upload(h_seg_dst, s));
-  HIPCHK(seg_arc.upload(h_seg_arc, s));
-  HIPCHK(m_src.upload(h_msrc, s));
-  HIPCHK(m_w.upload(h_mw, s));
-  HIPCHK(m_id.upload(h_mid, s));
-  HIPCHK(lvl_ent.upload(h_lvl_ent, s));
-  HIPCHK(ent_dst.upload(h_ent_dst, s));
-  HIPCHK(ent_arc.upload(h_ent_arc, s));
-  HIPCHK(e_src.upload(h_esrc, s));
-  HIPCHK(e_dst.upload(h_edst, s));
-  HIPCHK(e_w.upload(h_ew, s));
-  HIPCHK(e_id.upload(h_eid, s));
+  hipError_t err = hipSuccess;
+  // a table into a buffer of its own at the end of `pool` -> where it is on the device (nullptr: the table is empty)
+  auto up = [&](auto& pool, const auto& v) {
+    pool.emplace_back();
+    if (err == hipSuccess) err = pool.back().upload(v, s);
+    return pool.back().p;
+  };
+  T = DecodeTables{n_states, final_state, H.n_syms, up(tab_u32, H.m.sym_seg), up(tab_u32, H.m.seg_state), up(tab_u32, H.m.seg_arc),
+                   up(tab_u32, H.m.other), up(tab_f64, H.m.w), up(tab_u32, H.m.id), H.e.n_levels, H.eps_cyclic ? 1 : 0,
+                   up(tab_u32, H.e.lvl_ent), up(tab_u32, H.e.ent_state), up(tab_u32, H.e.ent_arc), up(tab_u32, H.e.other),
+                   up(tab_u32, H.e_dst), up(tab_f64, H.e.w), up(tab_u32, H.e.id), H.n_eps, up(tab_u32, H.e.st_ent)};
+  TO = DecodeOutTables{up(tab_u32, H.om.sym_seg), up(tab_u32, H.om.seg_state), up(tab_u32, H.om.seg_arc), up(tab_u32, H.om.other),
+                       up(tab_f64, H.om.w), up(tab_u32, H.om.id), up(tab_u32, H.oe.lvl_ent), up(tab_u32, H.oe.ent_state),
+                       up(tab_u32, H.oe.ent_arc), up(tab_u32, H.oe.other), up(tab_f64, H.oe.w), up(tab_u32, H.oe.id),
+                       up(tab_u8, H.oe.has)};
+  TP = DecodePairTables{up(tab_u32, H.m.osym), H.pe.n_levels, H.m.max_seg, up(tab_u32, H.pe.lvl_ent), up(tab_u32, H.pe.ent_state),
+                        up(tab_u32, H.pe.ent_arc), up(tab_u32, H.pe.other), up(tab_f64, H.pe.w), up(tab_u32, H.pe.id),
+                        up(tab_u32, H.pe.osym), up(tab_u32, H.pe.st_ent)};
+  TPO = DecodePairOutTables{TO.sym_seg, TO.seg_src, TO.seg_arc, TO.m_dst, TO.m_w, TO.m_id, up(tab_u32, H.om.osym), H.poe.n_levels,
+                            H.om.max_seg, up(tab_u32, H.poe.lvl_ent), up(tab_u32, H.poe.ent_state), up(tab_u32, H.poe.ent_arc),
+                            up(tab_u32, H.poe.other), up(tab_f64, H.poe.w), up(tab_u32, H.poe.id), up(tab_u32, H.poe.osym),
+                            up(tab_u8, H.poe.has)};
+  if (err != hipSuccess) return fail(CARMEL_HIP_ERR_HIP, std::string("upload_tables: ") + hipGetErrorString(err));
   HIPCHK(a_src.upload(src, s));
   HIPCHK(a_w.upload(logw, s));
-  HIPCHK(a_eps.upload(h_aeps, s));
-  HIPCHK(eps_in.upload(h_epsin, s));
-  HIPCHK(st_ent.upload(h_stent, s));
-  HIPCHK(o_sym_seg.upload(h_osym_seg, s));
-  HIPCHK(o_seg_src.upload(h_oseg_src, s));
-  HIPCHK(o_seg_arc.upload(h_oseg_arc, s));
-  HIPCHK(o_m_dst.upload(h_omdst, s));
-  HIPCHK(o_m_w.upload(h_omw, s));
-  HIPCHK(o_m_id.upload(h_omid, s));
-  HIPCHK(o_lvl_ent.upload(h_olvl_ent, s));
-  HIPCHK(o_ent_src.upload(h_oent_src, s));
-  HIPCHK(o_ent_arc.upload(h_oent_arc, s));
-  HIPCHK(o_e_dst.upload(h_oedst, s));
-  HIPCHK(o_e_w.upload(h_oew, s));
-  HIPCHK(o_e_id.upload(h_oeid, s));
-  HIPCHK(eps_out.upload(h_epsout, s));
-  HIPCHK(o_st_ent.upload(h_ostent, s));
+  HIPCHK(a_eps.upload(H.a_eps, s));
+  HIPCHK(a_flags.upload(H.a_flags, s));
+  HIPCHK(eps_in.upload(H.e.has, s));
   HIPCHK(hipStreamSynchronize(s));
-  TO = DecodeOutTables{o_sym_seg.p, o_seg_src.p, o_seg_arc.p, o_m_dst.p, o_m_w.p,  o_m_id.p,  o_lvl_ent.p,
-                       o_ent_src.p, o_ent_arc.p, o_e_dst.p,   o_e_w.p,   o_e_id.p, eps_out.p, o_st_ent.p};
-  TP = DecodePairTables{p_m_osym.p, (uint32_t)h_plvl_ent.size() - 1, max_seg, p_lvl_ent.p, p_ent_dst.p, p_ent_arc.p, p_e_src.p,
-                        p_e_w.p,    p_e_id.p, p_e_osym.p, p_st_ent.p};
-  TPO = DecodePairOutTables{o_sym_seg.p,  o_seg_src.p,  o_seg_arc.p, o_m_dst.p, o_m_w.p,   o_m_id.p,    po_m_osym.p,
-                            (uint32_t)h_polvl_ent.size() - 1, max_oseg, po_lvl_ent.p, po_ent_src.p, po_ent_arc.p, po_e_dst.p,
-                            po_e_w.p, po_e_id.p, po_e_osym.p, po_eps_out.p};
-  T = DecodeTables{Q, final_state, n_syms, sym_seg.p, seg_dst.p, seg_arc.p, m_src.p, m_w.p, m_id.p, n_levels, eps_cyclic ? 1 : 0,
-                   lvl_ent.p, ent_dst.p, ent_arc.p, e_src.p, e_dst.p, e_w.p, e_id.p, (uint32_t)eps.size(), st_ent.p};
   return CARMEL_HIP_OK;
 }
 

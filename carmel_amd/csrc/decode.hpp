@@ -2,19 +2,20 @@
 // samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip and
 // decode_pairs_sample.hip) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
-// the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built and
-// uploaded by carmel_hip_decoder::upload_tables (decode.hip); the trellis kernel the k-best decoder and the sum share is
-// decode_trellis.hpp.
+// the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built on
+// the host by build_decode_tables (decode_tables.hpp) and copied to the device by carmel_hip_decoder::upload_tables (decode.hip);
+// the trellis kernel the k-best decoder and the sum share is decode_trellis.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <deque>
 #include <functional>
 #include <string>
 #include <vector>
+#include "decode_tables.hpp"
 #include "engine.hpp"
 
 namespace carmel_hip {
-constexpr uint32_t kNone = 0xffffffffu;
 constexpr int kLanes = 64;
 constexpr uint32_t kLdsStates = 4096;  // two rows of |Q| doubles in 64 KiB of LDS (k-best: |Q| K doubles a row, |Q| K <= 4096)
 constexpr int kErrCycle = 1, kErrWalk = 2;
@@ -58,7 +59,6 @@ struct DecodeOutTables {
   const double* e_w;
   const uint32_t* e_id;
   const uint8_t* eps_out;    // [n_states]: an epsilon arc leaves the state
-  const uint32_t* st_ent;    // [n_states] -> the entry whose source the state is (kNone: no epsilon arc leaves it)
 };
 
 // What the pair decoder (decode_pairs.hip) adds to DecodeTables' matched arrays: the other side's symbol of every matched arc, and
@@ -131,31 +131,28 @@ struct carmel_hip_decoder {
   uint64_t n_arcs = 0;
   std::vector<uint32_t> src, dst, msym;  // msym: the matched-side symbol of every arc
   std::vector<double> logw;
-  bool eps_cyclic = false;
-  DevBuf<uint32_t> sym_seg, seg_dst, seg_arc, m_src, m_id, lvl_ent, ent_dst, ent_arc, e_src, e_dst, e_id, a_src, st_ent;
-  DevBuf<double> m_w, e_w, a_w;
-  DevBuf<uint8_t> a_eps;
-  DevBuf<uint8_t> eps_in;  // [|Q|]: the state is the destination of an epsilon arc of non-zero weight (k-best: its epsilon level is >= 1)
-  DecodeTables T;
-  // the outgoing view (DecodeOutTables), and the arc counts of a carmel_hip_decode_posterior or carmel_hip_decode_pairs_posterior call: zeroed once per call,
-  // accumulated over all its chunks
-  DevBuf<uint32_t> o_sym_seg, o_seg_src, o_seg_arc, o_m_dst, o_m_id, o_lvl_ent, o_ent_src, o_ent_arc, o_e_dst, o_e_id, o_st_ent;
-  DevBuf<double> o_m_w, o_e_w, count;
-  DevBuf<uint8_t> eps_out;
-  DecodeOutTables TO;
-  // the pair decoder's tables (decode_pairs.hip); pair_cycle: empty, or the 00 cycle that makes both pair entry points refuse
   std::vector<uint32_t> osym;  // the other side's symbol of every arc
-  DevBuf<uint32_t> p_m_osym, p_lvl_ent, p_ent_dst, p_ent_arc, p_e_src, p_e_id, p_e_osym, p_st_ent;
-  DevBuf<double> p_e_w;
+  bool eps_cyclic = false;
+  // the tables on the device, and the buffers that own them: one buffer per table, in the order upload_tables filled the four
+  // structs (a deque: a DevBuf frees its memory when destroyed and must not move)
+  DecodeTables T;
+  DecodeOutTables TO;        // the outgoing view
+  DecodePairTables TP;       // the pair decoders' tables (decode_pairs.hip)
+  DecodePairOutTables TPO;   // their outgoing view, for carmel_hip_decode_pairs_posterior
+  std::deque<DevBuf<uint32_t> > tab_u32;
+  std::deque<DevBuf<double> > tab_f64;
+  std::deque<DevBuf<uint8_t> > tab_u8;
+  // what the walks and the trellis launches take beside the structs: every arc's source and weight, dropped arcs too
+  DevBuf<uint32_t> a_src;
+  DevBuf<double> a_w;
+  DevBuf<uint8_t> a_eps;    // per arc: the matched symbol is epsilon
   DevBuf<uint8_t> a_flags;  // per arc, for the pair walk: bit 0 the matched symbol is not epsilon, bit 1 the other symbol is not
-  DecodePairTables TP;
-  // their outgoing view (DecodePairOutTables), for carmel_hip_decode_pairs_posterior
-  DevBuf<uint32_t> po_m_osym, po_lvl_ent, po_ent_src, po_ent_arc, po_e_dst, po_e_id, po_e_osym;
-  DevBuf<double> po_e_w;
-  DevBuf<uint8_t> po_eps_out;
-  DecodePairOutTables TPO;
+  DevBuf<uint8_t> eps_in;   // [|Q|]: the state is the destination of an epsilon arc of non-zero weight (k-best: its epsilon level is >= 1)
+  // the arc counts of a carmel_hip_decode_posterior or carmel_hip_decode_pairs_posterior call: zeroed once per call, accumulated
+  // over all its chunks
+  DevBuf<double> count;
   uint32_t pair_levels = 0;  // the highest 00 level
-  std::string pair_cycle;
+  std::string pair_cycle;    // empty, or the 00 cycle that makes the pair entry points refuse
   std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
   // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample, carmel_hip_decode_pairs_sample): every path's reported weight, the CSR
   // of the paths' arcs, the arcs
