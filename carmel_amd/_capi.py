@@ -47,6 +47,7 @@ SYMBOLS = [
     "carmel_hip_decode_pairs", "carmel_hip_decode_pairs_sum",
     "carmel_hip_decode_pairs_posterior",
     "carmel_hip_decode_pairs_sample",
+    "carmel_hip_decode_pairs_kbest",
 ]
 
 
@@ -244,6 +245,7 @@ def _load():
     lib.carmel_hip_decode_pairs_sum.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.carmel_hip_decode_pairs_posterior.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     lib.carmel_hip_decode_pairs_sample.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
+    lib.carmel_hip_decode_pairs_kbest.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp]
     for s in SYMBOLS:  # a prototype for every entry point: without one ctypes passes Python ints as C int (64-bit seeds
         if getattr(lib, s).argtypes is None:  # and bare handles would be truncated)
             raise ImportError("carmel_amd: no ctypes prototype for %s" % s)

@@ -1,6 +1,6 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
-// samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip and
-// decode_pairs_sample.hip) share: the prepared tables, the decoder
+// samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip,
+// decode_pairs_sample.hip and decode_pairs_kbest.hip) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built on
 // the host by build_decode_tables (decode_tables.hpp) and copied to the device by carmel_hip_decoder::upload_tables (decode.hip);
@@ -154,7 +154,8 @@ struct carmel_hip_decoder {
   uint32_t pair_levels = 0;  // the highest 00 level
   std::string pair_cycle;    // empty, or the 00 cycle that makes the pair entry points refuse
   std::vector<uint32_t> paths;  // the last decode's paths (arc ids, path order)
-  // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample, carmel_hip_decode_pairs_sample): every path's reported weight, the CSR
+  // the last k-best or sample call (carmel_hip_decode_kbest, carmel_hip_decode_sample, carmel_hip_decode_pairs_sample,
+  // carmel_hip_decode_pairs_kbest): every path's reported weight, the CSR
   // of the paths' arcs, the arcs
   std::vector<double> kb_logw;
   std::vector<uint64_t> kb_off;

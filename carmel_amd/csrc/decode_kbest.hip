@@ -35,27 +35,13 @@
 #include <cstring>
 #include <limits>
 #include <vector>
+#include "decode_kbest_list.hpp"
 #include "decode_trellis.hpp"
 #include "engine.hpp"
 
 namespace {
-constexpr uint32_t kMaxK = 1024;
-constexpr uint64_t kEpsTag = 1ull << 32;  // a candidate's tag: (0 matched, 1 epsilon) << 32 | arc id
-
-// the first rank r of the source list S (sorted, padded with -inf) whose candidate (S[r] + w, tag, r) comes after the candidate
-// picked last, (vl, tagl, rl); K if none does.  "After" is monotone in r: S is non-increasing and so is S[r] + w.
-__device__ inline uint32_t kb_next(const double* S, double w, uint32_t K, uint64_t tag, double vl, uint64_t tagl, uint32_t rl) {
-  uint32_t lo = 0, hi = K;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const double v = S[mid] + w;
-    if (v < vl || (v == vl && (tag > tagl || (tag == tagl && mid > rl))))
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  return lo;
-}
+// (kMaxK, a candidate's tag and kb_next, the bisection for an arc's next candidate: decode_kbest_list.hpp, which
+// decode_pairs_kbest.hip shares)
 
 // fill one node's list: the first K candidates of the matched arcs [m0, m1) (sources in row `prev`) and the epsilon arcs [e0, e1)
 // (sources in row `same`), into out / oarc / orank (the node's K slots)

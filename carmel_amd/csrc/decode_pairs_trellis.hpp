@@ -1,5 +1,6 @@
 // decode_pairs_trellis.hpp — what the pair entry points (decode_pairs.hip: the Viterbi alignment and the sum;
-// decode_pairs_posterior.hip: the arc posteriors; decode_pairs_sample.hip: the alignment samples) share: the anti-diagonal
+// decode_pairs_posterior.hip: the arc posteriors; decode_pairs_sample.hip: the alignment samples) share, and of which
+// decode_pairs_kbest.hip (the k best alignments: a k-list trellis kernel of its own) takes Diag and the host side: the anti-diagonal
 // trellis over (matched position i, other position j, state q) with its fixed candidate order, the sum's accumulator, the
 // accumulator that keeps every node (the forward pass of the posteriors and of the sampler), and the host side of a call -- the
 // argument checks, the tier and the global tier's diagonals.  The trellis, its order and its barriers are described in

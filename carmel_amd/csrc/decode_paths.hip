@@ -1,10 +1,11 @@
 // decode_paths.hip — what the batch decoders' entry points run on (declared in decode.hpp): the chunk driver of all of them
 // (carmel_hip_decode, carmel_hip_decode_kbest, carmel_hip_decode_sum, carmel_hip_decode_sample, carmel_hip_decode_posterior by a
 // line's length; carmel_hip_decode_pairs, carmel_hip_decode_pairs_sum, carmel_hip_decode_pairs_posterior and
-// carmel_hip_decode_pairs_sample by a pair's cost), for
+// carmel_hip_decode_pairs_sample and carmel_hip_decode_pairs_kbest by a pair's cost), for
 // the two that return the
 // paths of a path-recording trellis the walk kernel and the path driver around it, and the assembly of a chunk's paths that the
-// samplers (decode_sample.hip and decode_pairs_sample.hip, walks of their own) share with that driver.
+// samplers (decode_sample.hip and decode_pairs_sample.hip, walks of their own) and the pairs' k-best (decode_pairs_kbest.hip, a
+// ranked pair walk of its own) share with that driver.
 //
 // The walk: a path-recording trellis leaves, per (position i, state q, rank r), the arc that enters the slot's path last and the
 // rank of that arc's source (DecodePaths).  One lane per (line, rank j) follows them from (n, final, j) to (0, start, 0), once to

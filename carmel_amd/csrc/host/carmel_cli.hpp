@@ -109,6 +109,8 @@ struct Options {
   bool have_pair_counts = false;  // of the pairs as its weight (carmel_hip_decode_pairs_posterior), written to FILE
   long pair_samples = 0;          // --pair-samples=N: N alignments per pair drawn from the posterior over the pair's derivations
   bool have_pair_samples = false;  // (carmel_hip_decode_pairs_sample, seeded by -R), printed in place of the pair's best derivation
+  long pair_kbest = 0;            // --pair-kbest=N: the N best alignments of every pair (carmel_hip_decode_pairs_kbest), printed best
+  bool have_pair_kbest = false;   // first in place of the pair's best derivation; --kbest=N for the pairs of --pair-lines
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };

@@ -28,6 +28,10 @@
 // derivations, in sample order (carmel_hip_decode_pairs_sample, csrc/decode_pairs_sample.hip, seeded by -R), printed in place
 // of the best one with print_kbest's fill lines, N lines a pair; no Viterbi line is reported.  --pair-alignments=OUT then gets
 // one line per sample, N lines a pair (N empty lines for a pair without a derivation): sample s of pair l is line l N + s.
+// --pair-kbest=N is --kbest=N for the pairs (carmel's --post-b=FILE with -k n): every pair's N best derivations, best first
+// (carmel_hip_decode_pairs_kbest, csrc/decode_pairs_kbest.hip), printed in place of the best one with print_kbest's fill lines, N
+// lines a pair; the Viterbi line multiplies each pair's first path, as --kbest does, so N = 1 is plain --pair-lines -k 1 to the
+// byte.  --pair-alignments=OUT then gets N lines a pair: rank r of pair l is line l N + r, a missing rank an empty line.
 #include <cctype>
 #include "carmel_cli.hpp"
 using namespace carmel_host;
@@ -128,8 +132,12 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   const size_t n = lines.size();
   line_paths.assign(n + 1, 0);
   const auto t0 = std::chrono::steady_clock::now();
-  if (o.have_kbest || o.have_sample || o.have_pair_samples) {
-    if (o.have_pair_samples)
+  if (o.have_kbest || o.have_sample || o.have_pair_samples || o.have_pair_kbest) {
+    if (o.have_pair_kbest)
+      hip_check(carmel_hip_decode_pairs_kbest(d, (uint32_t)kbest, n, off.data(), sym.data(), off2.data(), sym2.data(),
+                                              line_paths.data()),
+                "carmel_hip_decode_pairs_kbest");
+    else if (o.have_pair_samples)
       hip_check(carmel_hip_decode_pairs_sample(d, (uint32_t)kbest, o.seed, n, off.data(), sym.data(), off2.data(), sym2.data(),
                                                line_paths.data()),
                 "carmel_hip_decode_pairs_sample");
@@ -167,7 +175,8 @@ void Batch::decode(carmel_hip_decoder* d, size_t kbest) {
   if (timing_on()) {
     double kms = 0;
     carmel_hip_decoder_last_ms(d, &kms);
-    std::cerr << (o.have_pair_samples ? "timing: pairs sample "
+    std::cerr << (o.have_pair_kbest     ? "timing: pairs kbest "
+                  : o.have_pair_samples ? "timing: pairs sample "
                   : o.have_sample     ? "timing: sample "
                   : o.have_pair_lines ? "timing: pairs "
                                       : "timing: decode ")
@@ -215,9 +224,10 @@ void Batch::sum_paths(carmel_hip_decoder* d) {
     if (sums[l] > kNegInf) prod_sum += sums[l];
 }
 
-// every pair's best path as in:out symbol names, one line a pair; with --pair-samples=N every sample, N lines a pair
+// every pair's best path as in:out symbol names, one line a pair; with --pair-samples=N every sample, with --pair-kbest=N every
+// rank, N lines a pair
 void Batch::pair_alignments() const {
-  const uint64_t per_pair = o.have_pair_samples ? (uint64_t)o.pair_samples : 1;
+  const uint64_t per_pair = o.have_pair_samples ? (uint64_t)o.pair_samples : o.have_pair_kbest ? (uint64_t)o.pair_kbest : 1;
   std::string buf;
   for (size_t l = 0; l < lines.size(); ++l)
     for (uint64_t r = 0; r < per_pair; ++r) {  // (a pair without a derivation: empty lines)
@@ -397,7 +407,8 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
     carmel_hip_decoder* d;
     ~Guard() { carmel_hip_decoder_destroy(d); }
   } guard{d};
-  const size_t kbest = o.have_pair_samples ? (size_t)o.pair_samples
+  const size_t kbest = o.have_pair_kbest     ? (size_t)o.pair_kbest
+                       : o.have_pair_samples ? (size_t)o.pair_samples
                        : o.have_sample     ? (size_t)o.sample_paths
                        : o.have_kbest      ? (size_t)o.kbest
                                            : 1;  // output lines per input line

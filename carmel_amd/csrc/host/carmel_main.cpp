@@ -37,7 +37,9 @@ static int print_help() {
                "the best paths as in:out symbol pairs, --pair-counts=FILE writes the composed machine with every arc's expected "
                "count over all derivations of the pairs as its weight (no cycles of *e*:*e* arcs), --pair-samples=N (N <= 65536) "
                "prints N alignments of every pair drawn from the posterior over its derivations in place of the best one, seeded "
-               "by -R, and --pair-alignments=OUT then gets one line per sample; "
+               "by -R, and --pair-alignments=OUT then gets one line per sample, --pair-kbest=N (N <= 1024) prints every pair's N best "
+               "alignments best first in place of the best one (--kbest=N for the pairs), and --pair-alignments=OUT then gets N "
+               "lines a pair; "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -65,6 +67,16 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
     if (o.pair_samples < 1 || o.pair_samples > 65536) throw UsageError("--pair-samples=N needs 1 <= N <= 65536");
     if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.pair_samples) throw UsageError("--pair-samples=N with -k m: m must be 1 or N");
   }
+  if (o.have_pair_kbest) {
+    if (with_pairs || o.train_cascade) throw UsageError("--pair-kbest=N with -t / --train-cascade / -S is not implemented");
+    if (!o.have_pair_lines) throw UsageError("--pair-kbest=N needs --pair-lines=FILE");
+    if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i']) throw UsageError("--pair-kbest=N applies to batch decoding (-b or -i)");
+    if (o.have_kbest) throw UsageError("--pair-kbest=N and --kbest=N exclude each other (--pair-kbest=N is --kbest=N for the pairs of --pair-lines)");
+    if (o.have_sample) throw UsageError("--pair-kbest=N and --sample-paths=N exclude each other");
+    if (o.have_pair_samples) throw UsageError("--pair-kbest=N and --pair-samples=N exclude each other");
+    if (o.pair_kbest < 1 || o.pair_kbest > 1024) throw UsageError("--pair-kbest=N needs 1 <= N <= 1024");
+    if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.pair_kbest) throw UsageError("--pair-kbest=N with -k m: m must be 1 or N");
+  }
   if (o.have_pair_alignments && !o.have_pair_lines) throw UsageError("--pair-alignments=OUT needs --pair-lines=FILE");
   if (o.have_pair_lines) {
     if (o.pair_lines.empty()) throw UsageError("--pair-lines=FILE needs a file name");
@@ -73,7 +85,7 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
     if (with_pairs) throw UsageError("--pair-lines=FILE with -t / --train-cascade / -S is not implemented");
     if (o.have_kbest || o.have_sample || o.have_posterior)
       throw UsageError("--pair-lines=FILE with --kbest=N, --sample-paths=N or --posterior-counts=FILE is not implemented (the pairs' "
-                       "arc posteriors: --pair-counts=FILE)");
+                       "k best alignments: --pair-kbest=N, their arc posteriors: --pair-counts=FILE)");
   }
   if (decoding) {
     if (o.have_sample) {
@@ -84,7 +96,7 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
     } else if (o.have_kbest) {
       if (o.kbest < 1 || o.kbest > 1024) throw UsageError("--kbest=N needs 1 <= N <= 1024");
       if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.kbest) throw UsageError("--kbest=N with -k m: m must be 1 or N");
-    } else if (!o.have_pair_samples) {  // (--pair-samples=N: -k is absent, 1 or N, checked above)
+    } else if (!o.have_pair_samples && !o.have_pair_kbest) {  // (--pair-samples=N, --pair-kbest=N: -k is absent, 1 or N, checked above)
       if (o.kpaths > 1)
         throw UsageError("-k n with n > 1 (k-best paths) is not implemented; -k 1 with -b or -i is; use --kbest=n");
       if (o.kpaths < 1) throw UsageError("-b / -i without -k 1 (printing each line's composition) is not implemented");

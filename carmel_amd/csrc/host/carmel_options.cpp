@@ -138,6 +138,10 @@ Options parse_args(int argc, char** argv) {
         o.pair_samples = std::atol(v.c_str());
         o.have_pair_samples = true;
       }
+      else if (k == "pair-kbest") {  // not a carmel option: the N best derivations of every pair (carmel_hip_decode_pairs_kbest)
+        o.pair_kbest = std::atol(v.c_str());
+        o.have_pair_kbest = true;
+      }
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")

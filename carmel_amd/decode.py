@@ -12,6 +12,7 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     sums = d.sum_pairs(lines, lines2)              # ln of every pair's sum over all its derivations (csrc/decode_pairs.hip)
     sums, counts = d.posterior_pairs(lines, lines2, weights=None)   # expected uses of every arc over the pairs' derivations
     weights, spaths = d.sample_pairs(lines, lines2, n, seed=0)      # n derivations per pair, each drawn with probability weight / sum
+    weights, kpaths = d.decode_pairs_kbest(lines, lines2, k)        # the k best alignments of every pair (csrc/decode_pairs_kbest.hip)
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -27,7 +28,11 @@ posterior_pairs posterior's: sum_pairs' sums, bit for bit, and the arcs' expecte
 (csrc/decode_pairs_posterior.hip: the pair trellis forwards and backwards).  sample_pairs returns sample's shapes: a pair with a
 derivation has exactly n alignments, in sample order, duplicates kept, each drawn from the posterior over the pair's derivations;
 sample s of pair l depends on the machine, the pair, the seed, l and s alone (csrc/decode_pairs_sample.hip: the forward planes of
-the arc posteriors and a backward sampling walk); sample_pairs_raw returns sample_raw's flat arrays."""
+the arc posteriors and a backward sampling walk); sample_pairs_raw returns sample_raw's flat arrays.  decode_pairs_kbest returns
+decode_kbest's shapes: per pair the reported ln weights and the arc ids of its min(k, number of derivations) best alignments,
+best first, 1 <= k <= 1024; rank 0 is decode_pairs' path and weight, and an insertion loop *e*:y is legal for every k
+(csrc/decode_pairs_kbest.hip: the pair trellis with a list of k values a node); decode_pairs_kbest_raw returns decode_kbest_raw's
+flat arrays."""
 import ctypes as C
 
 import numpy as np
@@ -166,6 +171,20 @@ class Decoder(object):
     def sample_pairs(self, lines, lines2, n, seed=0):
         """-> (weights, paths) shaped as sample's: per pair its n sampled derivations (none: no derivation)"""
         return self._per_line(len(lines), *self.sample_pairs_raw(lines, lines2, n, seed))
+
+    def decode_pairs_kbest_raw(self, lines, lines2, k):
+        """-> (line_paths, logw, path_off, arcs): the arrays of carmel_hip_decode_pairs_kbest / carmel_hip_decoder_get_kbest"""
+        assert len(lines) == len(lines2)
+        off, sym = _pack(lines)
+        off2, sym2 = _pack(lines2)
+        line_paths = np.zeros(len(lines) + 1, np.uint64)
+        check(lib.carmel_hip_decode_pairs_kbest(self._h, int(k), len(lines), ptr(off), ptr(sym), ptr(off2), ptr(sym2),
+                                                ptr(line_paths)), "carmel_hip_decode_pairs_kbest")
+        return self._last_paths(line_paths)
+
+    def decode_pairs_kbest(self, lines, lines2, k):
+        """-> (weights, paths) shaped as decode_kbest's: per pair its min(k, number of derivations) best alignments, best first"""
+        return self._per_line(len(lines), *self.decode_pairs_kbest_raw(lines, lines2, k))
 
     def posterior(self, lines, weights=None):
         """-> (sums, counts): sum(lines), and per arc its expected number of uses over the derivations of the lines (line l counts

@@ -695,6 +695,27 @@ int carmel_hip_decode_pairs_posterior(carmel_hip_decoder* d, uint64_t n_pairs, c
  * the forward kernel and both passes of the walk. */
 int carmel_hip_decode_pairs_sample(carmel_hip_decoder* d, uint32_t n_samples, uint64_t seed, uint64_t n_pairs, const uint64_t* off,
                                    const uint32_t* sym, const uint64_t* off2, const uint32_t* sym2, uint64_t* line_paths);
+/* ---- batch pair k-best alignments (carmel --post-b=FILE -k n; csrc/decode_pairs_kbest.hip) ----
+ * Replaces: --post-b with -k n -- post_compose's second composition with the parallel line (carmel.cc:569-597) handed to
+ * print_kbest(k, result) (carmel.cc:379-397, WFST::visit_kbest, fst.h:791, kbest.h).  Pairs and derivations as
+ * carmel_hip_decode_pairs defines them.  Pair l gets its min(k, number of derivations) best derivations -- paths line_paths[l] ..
+ * line_paths[l + 1] (line_paths: n_pairs + 1 entries) of carmel_hip_decoder_kbest_size / carmel_hip_decoder_get_kbest, exactly
+ * as after carmel_hip_decode_kbest -- greatest value first.  Two derivations differ if their arc-id sequences differ.  A
+ * derivation's VALUE, by which the paths are chosen and ordered, is its arcs' logs added in path order from the start, in f64.
+ * The trellis is carmel_hip_decode_pairs' with a list of k values per (position in x, position in y, state): a candidate is (arc
+ * a into the state, rank r in the list of a's source node), value list[source][r] + w(a), and candidates are ordered by value,
+ * descending; then arcs whose matched symbol is not epsilon before arcs whose matched symbol is epsilon; then lower arc id; then
+ * lower r.  The order is total: results do not depend on chunking, memory tier or launch order, and rank 0 of a pair
+ * is the very path and weight carmel_hip_decode_pairs returns.  The weight REPORTED for a path is its arcs' logs added from the
+ * END, as there: a pair's reported weights may therefore fail to be monotone in the last bit.  1 <= k <= 1024, else
+ * CARMEL_HIP_ERR_ARG ("k must be in 1 .. 1024"); a null d, off, off2 or line_paths, bad offsets on either side, or n_pairs >=
+ * 2^32: CARMEL_HIP_ERR_ARG.  An insertion loop *e*:y, which carmel_hip_decode_kbest must refuse for k > 1 as an epsilon cycle of
+ * the matched side, is an ordinary arc here for every k; a cycle of arcs with epsilon on both sides fails with
+ * CARMEL_HIP_ERR_UNSUPPORTED, naming the cycle, nothing is written and the handle stays usable.  May alternate with the other
+ * decode entry points on one handle, and sees the weights of carmel_hip_decoder_set_weights; carmel_hip_decoder_last_ms covers
+ * the trellis kernel and both passes of the walk. */
+int carmel_hip_decode_pairs_kbest(carmel_hip_decoder* d, uint32_t k, uint64_t n_pairs, const uint64_t* off, const uint32_t* sym,
+                                  const uint64_t* off2, const uint32_t* sym2, uint64_t* line_paths);
 
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
