@@ -226,6 +226,7 @@ int carmel_hip_decoder_set_weights(carmel_hip_decoder* d, const double* logw) {
   if (!d || (d->n_arcs && !logw)) return fail(CARMEL_HIP_ERR_ARG, "carmel_hip_decoder_set_weights: bad argument");
   HIPCHK(hipSetDevice(d->device));
   d->logw.assign(logw, logw + d->n_arcs);
+  d->gen_ready = false;  // (the generation tables hold the old weights' sums: the next carmel_hip_decoder_generate rebuilds them)
   return d->upload_tables();  // (which arcs have weight zero may have changed)
 }
 

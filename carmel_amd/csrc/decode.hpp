@@ -1,6 +1,6 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
 // samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip,
-// decode_pairs_sample.hip and decode_pairs_kbest.hip) share: the prepared tables, the decoder
+// decode_pairs_sample.hip and decode_pairs_kbest.hip; generation, decode_generate.hip, takes the handle and the path store) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built on
 // the host by build_decode_tables (decode_tables.hpp) and copied to the device by carmel_hip_decoder::upload_tables (decode.hip);
@@ -12,6 +12,7 @@
 #include <functional>
 #include <string>
 #include <vector>
+#include "decode_generate_tables.hpp"
 #include "decode_tables.hpp"
 #include "engine.hpp"
 
@@ -122,6 +123,16 @@ struct DecodePaths {
   int* err;
   uint32_t K;
 };
+
+// The generation tables on the device (decode_generate_tables.hpp), one per mode.  Joint: st_grp is nullptr and list q is state
+// q's.  Conditional: state q's groups are st_grp[q] .. st_grp[q + 1], each a list.  List g is arcs list_arc[g] .. list_arc[g + 1].
+struct GenerateTables {
+  const uint32_t* st_grp;    // [n_states + 1], or nullptr
+  const uint32_t* list_arc;  // [n_lists + 1]
+  const uint32_t* id;        // per arc of a list: its id, its destination, its cumulative value
+  const uint32_t* dst;
+  const double* cum;
+};
 }  // namespace carmel_hip
 
 struct carmel_hip_decoder {
@@ -160,6 +171,12 @@ struct carmel_hip_decoder {
   std::vector<double> kb_logw;
   std::vector<uint64_t> kb_off;
   std::vector<uint32_t> kb_arcs;
+  // the generation tables (decode_generate_tables.hpp; carmel_hip_decoder_generate, decode_generate.hip): built and copied by the
+  // first generate call, dropped by carmel_hip_decoder_set_weights
+  bool gen_ready = false;
+  carmel_hip::GenerateTables GJ, GC;  // joint: a list per state; conditional: a state's groups, a list per group
+  DevBuf<uint32_t> gen_u32[7];
+  DevBuf<double> gen_f64[2];
   double last_ms = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -2,7 +2,7 @@
 // transducer, each drawn with probability P(d | x) = w(d) / (the sum over all derivations of x), independently.  It stands
 // beside the best derivation (decode.hip), the K best (decode_kbest.hip) and the sum of all (decode_sum.hip); it is NOT the
 // reference's -G n, which walks the whole machine forward by locally normalised arc weights and retries on dead ends
-// (fst.h:708-757, carmel.cc:1446-1458) and stays refused.  Forward pass and backward sampling: the forward pass is decode_sum.hip's
+// (fst.h:708-757, carmel.cc:1446-1458): that is decode_generate.hip.  Forward pass and backward sampling: the forward pass is decode_sum.hip's
 // (the same node arithmetic, decode_sum_node.hpp, in decode_trellis.hpp's kernel) but keeps every row; the walk samples an arc
 // into the node it stands on with probability proportional to (the source node's forward value) x (the arc's weight).
 // Derivation, matched side, dropped zero-weight arcs, the empty line, unknown symbols: decode_kbest.hip's and decode_sum.hip's.

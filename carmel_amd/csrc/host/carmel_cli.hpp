@@ -111,6 +111,11 @@ struct Options {
   bool have_pair_samples = false;  // (carmel_hip_decode_pairs_sample, seeded by -R), printed in place of the pair's best derivation
   long pair_kbest = 0;            // --pair-kbest=N: the N best alignments of every pair (carmel_hip_decode_pairs_kbest), printed best
   bool have_pair_kbest = false;   // first in place of the pair's best derivation; --kbest=N for the pairs of --pair-lines
+  // --generate-paths=N (carmel's -G N) / --generate-pairs=N (carmel's -g N): N random paths / (input, output) pairs drawn from the
+  // composed machine itself (carmel_hip_decoder_generate, seeded by -R); --generate-max-arcs=L is carmel's -L, --generate-tries=T
+  // bounds the attempts a path may take
+  long generate_paths = 0, generate_pairs = 0, generate_max_arcs = 1000, generate_tries = 256;
+  bool have_generate_paths = false, have_generate_pairs = false, have_generate_max_arcs = false, have_generate_tries = false;
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };
@@ -178,6 +183,7 @@ void create_trainer(Job& j);
 int score_pairs(Job& j);
 void begin_training(Job& j);
 int decode_batch(const Options& o, carmel_host::Transducer& M, const std::string& text, int ws, bool quiet, int device);  // carmel_decode.cpp
+int generate_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
 void log_lattice_stats(const carmel_hip_lattice_stats& ls, size_t n);      // carmel_em.cpp
 void train_em(Job& j, const Options& iteration_controls);
 int train_gibbs(Job& j);                                                   // carmel_gibbs.cpp

@@ -7,7 +7,8 @@
 // (carmel_hip_decode_kbest, csrc/decode_kbest.hip); the summary multiplies each line's first path, as with -k 1.
 // --sample-paths=N prints, for every line, N derivations drawn from the posterior over its derivations, in sample order
 // (carmel_hip_decode_sample, csrc/decode_sample.hip, seeded by -R), in the same format and with the same fill lines; no best path
-// is computed, so the report has no Viterbi line.  It is not carmel's -G, which generates from the whole machine.
+// is computed, so the report has no Viterbi line.  It is not carmel's -G, which generates from the whole machine: that is
+// --generate-paths=N, at the end of this file.
 // --sum-paths (carmel's --sum) adds every line's sum of all paths (post_compose's sum_acyclic_paths, carmel.cc:555-599; carmel_hip_decode_sum,
 // csrc/decode_sum.hip) to the report on stderr; what goes to stdout does not change.
 // --posterior-counts=FILE writes the composed machine to FILE as Transducer::to_text does (-H / -J apply), every arc's weight
@@ -69,7 +70,7 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   void posterior_counts(carmel_hip_decoder* d) const;
   void pair_counts(carmel_hip_decoder* d) const;
   void write_counts(std::vector<double>& count, const char* option, const std::string& file) const;
-  void format_path(uint64_t p, std::string& buf) const;
+  void format_path(uint64_t p, std::string& buf, bool pair_form = false) const;
   void print_paths(size_t kbest, bool quiet);
   void log_ppx(double n_pairs, double prod, size_t n_0) const;
   void report() const;
@@ -288,9 +289,9 @@ void Batch::write_counts(std::vector<double>& count, const char* option, const s
   if (!of) throw std::runtime_error(std::string(option) + ": cannot write " + file);
 }
 
-// one path of a line into buf, as path_print writes it
-void Batch::format_path(uint64_t p, std::string& buf) const {
-  const bool fO = o.flags[(unsigned)'O'], fQ = o.flags[(unsigned)'Q'], fAT = o.flags[(unsigned)'@'], fW = o.flags[(unsigned)'W'],
+// one path of a line into buf, as path_print writes it; pair_form: the two lines of -@ whatever the switches say
+void Batch::format_path(uint64_t p, std::string& buf, bool pair_form) const {
+  const bool fO = o.flags[(unsigned)'O'], fQ = o.flags[(unsigned)'Q'], fAT = o.flags[(unsigned)'@'] || pair_form, fW = o.flags[(unsigned)'W'],
              fE = o.flags[(unsigned)'E'];
   auto name = [&](bool output, uint32_t id) -> std::string {
     const std::string& x = output ? M.out_syms.names[id] : M.in_syms.names[id];
@@ -419,5 +420,55 @@ int decode_batch(const Options& o, Transducer& M, const std::string& text, int w
   b.print_paths(kbest, quiet);
   if (o.have_pair_alignments) b.pair_alignments();
   b.report();
+  return 0;
+}
+
+// --generate-paths=N (carmel's -G N, carmel.cc:1446-1458) and --generate-pairs=N (carmel's -g N, carmel.cc:1459-1482): N random
+// walks through the composed machine (carmel_hip_decoder_generate, csrc/decode_generate.hip, seeded by -R; --generate-max-arcs=L
+// and --generate-tries=T are its limits).  There is no line stream.  A path prints as a decoded one does, one line in the -I / -O
+// forms (-Q -W -E apply) or, with -@, as the pair it spells (print_training_pair, fst.h:941); a pair prints as printSeq does
+// (carmel.cc:118-124): a line of input symbols and a line of output symbols, epsilons dropped.
+int generate_batch(const Options& o, Transducer& M, int ws, int device) {
+  Batch b{o, M, ws};
+  std::vector<uint32_t> src, dst, in, out, group;
+  std::vector<double> logw;
+  M.flatten(src, dst, in, out, logw, group);
+  carmel_hip_decoder* d = 0;
+  hip_check(carmel_hip_decoder_create(&d, device, (uint32_t)M.states.size(), M.final_state, logw.size(), src.data(), dst.data(),
+                                      in.data(), out.data(), logw.data(), 0),
+            "carmel_hip_decoder_create");
+  struct Guard {
+    carmel_hip_decoder* d;
+    ~Guard() { carmel_hip_decoder_destroy(d); }
+  } guard{d};
+  const bool pairs = o.have_generate_pairs;
+  const uint64_t n = (uint64_t)(pairs ? o.generate_pairs : o.generate_paths);
+  const auto t0 = std::chrono::steady_clock::now();
+  hip_check(carmel_hip_decoder_generate(d, pairs ? CARMEL_HIP_GENERATE_CONDITIONAL : CARMEL_HIP_GENERATE_JOINT, n, 0, o.seed,
+                                        (uint32_t)o.generate_max_arcs, (uint32_t)o.generate_tries, nullptr),
+            "carmel_hip_decoder_generate");
+  uint64_t n_paths = 0, n_path_arcs = 0;
+  hip_check(carmel_hip_decoder_kbest_size(d, &n_paths, &n_path_arcs), "carmel_hip_decoder_kbest_size");
+  b.best.resize(std::max<uint64_t>(n_paths, 1));
+  b.path_off.resize(n_paths + 1);
+  b.path.resize(std::max<uint64_t>(n_path_arcs, 1));
+  hip_check(carmel_hip_decoder_get_kbest(d, b.best.data(), b.path_off.data(), b.path.data()), "carmel_hip_decoder_get_kbest");
+  if (timing_on()) {
+    double kms = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    std::cerr << "timing: generate " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s (kernels "
+              << kms * 1e-3 << " s)\n";
+  }
+  for (auto& st : M.states)
+    for (auto& a : st) b.arc_of.push_back(&a);
+  std::string buf;
+  for (uint64_t p = 0; p < n_paths; ++p) {
+    b.format_path(p, buf, pairs);
+    if (buf.size() >= (1u << 20)) {
+      std::cout << buf;
+      buf.clear();
+    }
+  }
+  std::cout << buf << std::flush;
   return 0;
 }

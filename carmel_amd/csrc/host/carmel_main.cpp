@@ -40,6 +40,10 @@ static int print_help() {
                "by -R, and --pair-alignments=OUT then gets one line per sample, --pair-kbest=N (N <= 1024) prints every pair's N best "
                "alignments best first in place of the best one (--kbest=N for the pairs), and --pair-alignments=OUT then gets N "
                "lines a pair; "
+               "generation from the composed machine itself, seeded by -R: --generate-paths=N (carmel's -G N) prints N random paths, "
+               "one line each, with -I / -O (-Q -W -E) or two lines each with -@; --generate-pairs=N (carmel's -g N) prints N random "
+               "input/output pairs, two lines each; --generate-max-arcs=L (carmel's -L, default 1000) bounds a path's arcs and "
+               "--generate-tries=T (default 256) the attempts a path may take; "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -113,6 +117,43 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
   return decoding;
 }
 
+// generation (--generate-paths=N / --generate-pairs=N: carmel's -G / -g): usage errors name the switch, before any device call;
+// true: generating
+static bool validate_generation(const Options& o) {
+  const bool generating = o.have_generate_paths || o.have_generate_pairs;
+  if (!generating) {
+    if (o.have_generate_max_arcs) throw UsageError("--generate-max-arcs=L applies to --generate-paths=N or --generate-pairs=N");
+    if (o.have_generate_tries) throw UsageError("--generate-tries=T applies to --generate-paths=N or --generate-pairs=N");
+    return false;
+  }
+  if (o.have_generate_paths && o.have_generate_pairs) throw UsageError("--generate-paths=N and --generate-pairs=N exclude each other");
+  const char* sw = o.have_generate_paths ? "--generate-paths=N" : "--generate-pairs=N";
+  const long n = o.have_generate_paths ? o.generate_paths : o.generate_pairs;
+  if (n < 1 || (unsigned long long)n > (1ull << 32)) throw UsageError(std::string(sw) + " needs 1 <= N <= 2^32");
+  if (o.generate_max_arcs < 1 || o.generate_max_arcs > (1l << 20))
+    throw UsageError(std::string(sw) + ": --generate-max-arcs=L needs 1 <= L <= 2^20 (1048576)");
+  if (o.generate_tries < 1 || o.generate_tries > 65536) throw UsageError(std::string(sw) + ": --generate-tries=T needs 1 <= T <= 65536");
+  if ((unsigned long long)o.generate_max_arcs * (unsigned long long)o.generate_tries > (1ull << 24))
+    throw UsageError(std::string(sw) + ": --generate-max-arcs=L times --generate-tries=T must be at most 2^24 (16777216)");
+  auto with = [&](bool on, const char* what) {
+    if (on) throw UsageError(std::string(sw) + " with " + what + " is not implemented: it generates from the composed machine, without lines or a corpus");
+  };
+  with(o.flags[(unsigned)'b'], "-b");
+  with(o.flags[(unsigned)'i'], "-i");
+  with(o.flags[(unsigned)'s'], "-s");
+  with(o.kpaths != 0, "-k");
+  with(o.have_kbest, "--kbest=N");
+  with(o.have_sample, "--sample-paths=N");
+  with(o.have_pair_lines, "--pair-lines=FILE");
+  with(o.crp, "--crp");
+  with(o.train_cascade, "--train-cascade");
+  with(o.flags[(unsigned)'t'], "-t");
+  with(o.flags[(unsigned)'S'], "-S");
+  if (o.have_generate_paths && !o.flags[(unsigned)'I'] && !o.flags[(unsigned)'O'] && !o.flags[(unsigned)'@'])
+    throw UsageError("--generate-paths=N without -I, -O or -@ (the arc path form) is not implemented");
+  return true;
+}
+
 // the line stream: stdin with -s, else the first file (the last with -r) (carmel.cc:1099-1115, 1186-1191)
 static std::string read_line_stream(Options& o) {
   if (o.flags[(unsigned)'s']) {
@@ -157,6 +198,7 @@ static int run(int argc, char** argv) {
   const bool scoring = !training && o.flags[(unsigned)'S'];  // carmel.cc:1134: -t overrides -S
   const bool with_pairs = training || scoring;
   if (o.flags[(unsigned)'h']) return print_help();
+  const bool generating = validate_generation(o);
   const bool decoding = validate_decoding(o, with_pairs);
   const std::string line_text = decoding ? read_line_stream(o) : std::string();
   if (o.files.empty() || (with_pairs && o.files.size() < 2)) {
@@ -175,6 +217,7 @@ static int run(int argc, char** argv) {
   if (int rc = load_members(j)) return rc;
   if (int rc = compose_members(j)) return rc;
   if (decoding) return decode_batch(o, *j.result, line_text, j.wstyle, j.quiet, o.gpu);
+  if (generating) return generate_batch(o, *j.result, j.wstyle, o.gpu);
   if (!with_pairs) return print_composition(j);
   read_corpus(j, corpus_text, /*weight_lines=*/!scoring);
   create_trainer(j);

@@ -142,6 +142,22 @@ Options parse_args(int argc, char** argv) {
         o.pair_kbest = std::atol(v.c_str());
         o.have_pair_kbest = true;
       }
+      else if (k == "generate-paths") {  // carmel's -G N under another name (carmel.cc:1446-1458): -G itself stays refused, below
+        o.generate_paths = std::atol(v.c_str());
+        o.have_generate_paths = true;
+      }
+      else if (k == "generate-pairs") {  // carmel's -g N (carmel.cc:1459-1482)
+        o.generate_pairs = std::atol(v.c_str());
+        o.have_generate_pairs = true;
+      }
+      else if (k == "generate-max-arcs") {  // carmel's -L n: here the most arcs a generated path may have, in both modes
+        o.generate_max_arcs = std::atol(v.c_str());
+        o.have_generate_max_arcs = true;
+      }
+      else if (k == "generate-tries") {  // not a carmel option: the attempts a path may take (the reference retries for ever)
+        o.generate_tries = std::atol(v.c_str());
+        o.have_generate_tries = true;
+      }
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")
@@ -248,6 +264,9 @@ Options parse_args(int argc, char** argv) {
             o.plus_alpha = std::atof(value());
             o.plus_alpha_set = true;
             break;
+          case 'g': throw UsageError("switch -g n is not implemented under that name; use --generate-pairs=n");
+          case 'G': throw UsageError("switch -G n is not implemented under that name; use --generate-paths=n");
+          case 'L': throw UsageError("switch -L n is not implemented under that name; use --generate-max-arcs=n");
           default:
             // switches without a value that this front end implements; everything else carmel knows (k-best, generation,
             // projection, pruning, OpenFst, ...) is outside the training path

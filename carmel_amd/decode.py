@@ -13,6 +13,8 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     sums, counts = d.posterior_pairs(lines, lines2, weights=None)   # expected uses of every arc over the pairs' derivations
     weights, spaths = d.sample_pairs(lines, lines2, n, seed=0)      # n derivations per pair, each drawn with probability weight / sum
     weights, kpaths = d.decode_pairs_kbest(lines, lines2, k)        # the k best alignments of every pair (csrc/decode_pairs_kbest.hip)
+    paths = d.generate(n, mode="joint", seed=0)    # n random paths drawn from the machine itself (carmel -G n; csrc/decode_generate.hip)
+    pairs = d.generate_pairs(n, seed=0)            # n random (input, output) strings (carmel -g n: mode "conditional")
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -32,12 +34,21 @@ the arc posteriors and a backward sampling walk); sample_pairs_raw returns sampl
 decode_kbest's shapes: per pair the reported ln weights and the arc ids of its min(k, number of derivations) best alignments,
 best first, 1 <= k <= 1024; rank 0 is decode_pairs' path and weight, and an insertion loop *e*:y is legal for every k
 (csrc/decode_pairs_kbest.hip: the pair trellis with a list of k values a node); decode_pairs_kbest_raw returns decode_kbest_raw's
-flat arrays."""
+flat arrays.
+generate draws from the model, not from a line's posterior: a forward random walk from state 0 that stops the first time it
+reaches the final state, an arc chosen with probability weight / (the weights leaving the state) in mode "joint", and in mode
+"conditional" first one of the state's matched-side symbols uniformly, then an arc among that symbol's by weight; a walk that
+meets a dead end or max_arcs arcs is drawn again, max_tries times at most (CarmelHipError otherwise).  Path p of a call is path
+first + p of the stream of (seed, mode): it does not depend on how the stream is cut into calls (include/carmel_hip.h has the
+rule in full)."""
 import ctypes as C
 
 import numpy as np
 
 from ._capi import check, f64, lib, ptr, u32, u64
+
+
+GENERATE_MODES = {"joint": 0, "conditional": 1}  # CARMEL_HIP_GENERATE_JOINT (carmel -G), CARMEL_HIP_GENERATE_CONDITIONAL (carmel -g)
 
 
 def _pack(lines):
@@ -185,6 +196,27 @@ class Decoder(object):
     def decode_pairs_kbest(self, lines, lines2, k):
         """-> (weights, paths) shaped as decode_kbest's: per pair its min(k, number of derivations) best alignments, best first"""
         return self._per_line(len(lines), *self.decode_pairs_kbest_raw(lines, lines2, k))
+
+    def generate_raw(self, n, mode="joint", seed=0, max_arcs=1000, max_tries=256, first=0):
+        """-> (logw, path_off, arcs, tries): n random paths through the machine (carmel_hip_decoder_generate), path p being path
+        first + p of the stream of (seed, mode); tries[p] the attempts it took"""
+        n = int(n)
+        tries = np.zeros(max(n, 1), np.uint32)
+        check(lib.carmel_hip_decoder_generate(self._h, GENERATE_MODES[mode], n, int(first), int(seed), int(max_arcs), int(max_tries),
+                                              ptr(tries)), "carmel_hip_decoder_generate")
+        _, logw, path_off, arcs = self._last_paths(np.array([0, n], np.uint64))
+        return logw, path_off, arcs, tries[:n]
+
+    def generate(self, n, mode="joint", seed=0, max_arcs=1000, max_tries=256, first=0):
+        """-> [(ln weight, [arc ids])]: n random paths (carmel -G n; mode "conditional": the paths behind carmel -g n)"""
+        logw, path_off, arcs, _ = self.generate_raw(n, mode, seed, max_arcs, max_tries, first)
+        return [(float(logw[p]), [int(a) for a in arcs[int(path_off[p]):int(path_off[p + 1])]]) for p in range(len(logw))]
+
+    def generate_pairs(self, n, mode="conditional", seed=0, max_arcs=1000, max_tries=256, first=0):
+        """-> [(input symbols, output symbols)]: the two strings of n random paths, epsilons dropped (carmel -g n)"""
+        isym, osym = self._keep[2], self._keep[3]
+        return [([int(isym[a]) for a in path if isym[a]], [int(osym[a]) for a in path if osym[a]])
+                for _, path in self.generate(n, mode, seed, max_arcs, max_tries, first)]
 
     def posterior(self, lines, weights=None):
         """-> (sums, counts): sum(lines), and per arc its expected number of uses over the derivations of the lines (line l counts

@@ -591,7 +591,7 @@ int carmel_hip_decode_sum(carmel_hip_decoder* d, uint64_t n_lines, const uint64_
  * weight of all): for every line, n_samples derivations drawn independently with probability w(d) / (the sum over all
  * derivations of the line), derivations as carmel_hip_decode_kbest defines them.  It replaces nothing of the reference: carmel's
  * -G n (fst.h:708-757, carmel.cc:1446-1458) generates from the whole machine by locally normalised arc weights, retrying on dead
- * ends, and is not this.  Lines as for carmel_hip_decode.  A line without a derivation gets no paths, every other line exactly
+ * ends: that is carmel_hip_decoder_generate, below.  Lines as for carmel_hip_decode.  A line without a derivation gets no paths, every other line exactly
  * n_samples -- paths line_paths[l] .. line_paths[l + 1] (line_paths: n_lines + 1 entries) of carmel_hip_decoder_kbest_size /
  * carmel_hip_decoder_get_kbest -- in sample order, duplicates kept; a path's reported weight is its arcs' logs added from the
  * END, as there.  The forward pass is carmel_hip_decode_sum's, bit for bit, with every row kept; sample s of line l walks back
@@ -716,6 +716,45 @@ int carmel_hip_decode_pairs_sample(carmel_hip_decoder* d, uint32_t n_samples, ui
  * the trellis kernel and both passes of the walk. */
 int carmel_hip_decode_pairs_kbest(carmel_hip_decoder* d, uint32_t k, uint64_t n_pairs, const uint64_t* off, const uint32_t* sym,
                                   const uint64_t* off2, const uint32_t* sym2, uint64_t* line_paths);
+
+/* ---- batch generation: random paths and pairs drawn from the machine itself (carmel -G n / -g n; csrc/decode_generate.hip) ----
+ * Replaces: -G n, WFST::randomPath (fst.h:708-757, carmel.cc:1446-1458) -- mode CARMEL_HIP_GENERATE_JOINT -- and -g n,
+ * WFST::generate (fst.cc:24-79, carmel.cc:1459-1482; printSeq, carmel.cc:118-124; print_training_pair, fst.h:941) -- mode
+ * CARMEL_HIP_GENERATE_CONDITIONAL.  A forward random walk over the whole machine; no lines are given.  The rule:
+ * Arcs.  Only arcs of weight > 0 (log weight > -inf) exist for generation.
+ * Lists.  JOINT mode has one list per state: its arcs by arc id.  CONDITIONAL mode has one list per (state, matched-side symbol):
+ * that group's arcs by arc id; a state's groups are in ascending symbol id, epsilon (0) first; the matched side is the handle's
+ * `side`, so side 0 is carmel's -g.
+ * Cumulative values of a list w_0 .. w_{m-1}.  M = max w_k; p_k = exp(w_k - M), by the host's std::exp; cum_k = cum_{k-1} + p_k in
+ * f64, in list order; S = cum_{m-1}.
+ * Choice with a uniform u.  t = u S, one f64 multiply.  The arc is the first k with cum_k > t; if there is none, because t rounded
+ * up to S, the arc is the first k with cum_k == S.  An arc whose p_k underflowed to 0 is therefore never chosen.  The device finds
+ * k by bisection; it never scans.
+ * Attempt a = 0, 1, ... of path P (P is its index in the stream, first_path + its index in the call).  Start with s = 0, n = 0,
+ * and repeat: 1. if s is the final state, accept; 2. if n == max_arcs, or s has no list, reject; 3. choose an arc -- JOINT:
+ * u = carmel_hip_gibbs_uniform(seed, a, P, n), chosen in s's list; CONDITIONAL: G is the number of s's groups,
+ * g = min(G - 1, floor(carmel_hip_gibbs_uniform(seed, a, P, 2n) G)), and the arc is chosen in group g with
+ * carmel_hip_gibbs_uniform(seed, a, P, 2n + 1); 4. append the arc, set s to its destination, increment n.  The final state is
+ * tested before the cap, so a path of exactly max_arcs arcs is accepted.  A rejected attempt is followed by a + 1; after max_tries
+ * rejected attempts the path has failed.  A path depends on (machine, weights, side, mode, seed, P, max_arcs) alone: not on
+ * chunking, launch order, the other paths, or how a stream is cut into calls.
+ * Reported weight.  As everywhere in the decoders, the path's arcs' logs added from the END, w1 + (w2 + (... + (wn + 0))); the
+ * empty path has 0.0.
+ * Deviations from the reference: the stateless generator (the reference draws from one sequential stream); groups in symbol
+ * order where the reference walks a hash table; > where the reference has >=; max_arcs counts arcs for both modes, where -L
+ * counts symbols a side for -g and does not bind -G; a bounded number of retries, where the reference retries for ever.
+ * The call returns exactly n_paths paths, in order, read with carmel_hip_decoder_kbest_size / carmel_hip_decoder_get_kbest;
+ * tries[p] (if not null) is the number of attempts path p used, at least 1.  CARMEL_HIP_ERR_ARG: a null handle, an unknown mode,
+ * first_path + n_paths > 2^32, max_arcs outside 1 .. 2^20, max_tries outside 1 .. 65536, max_arcs max_tries > 2^24.  n_paths = 0
+ * succeeds with no paths.  A failed path gives CARMEL_HIP_ERR_STATE: the message names the lowest failed P and the limits, and
+ * the handle's previous results (and tries) are left as they were.  Epsilon cycles and 00 cycles are legal here: a lane's work is
+ * bounded by max_arcs max_tries.  May alternate with every other entry point on one handle, and sees the weights of
+ * carmel_hip_decoder_set_weights (its tables are built on the first call and dropped there); carmel_hip_decoder_last_ms covers
+ * both passes of the walk. */
+#define CARMEL_HIP_GENERATE_JOINT 0        /* carmel -G */
+#define CARMEL_HIP_GENERATE_CONDITIONAL 1  /* carmel -g */
+int carmel_hip_decoder_generate(carmel_hip_decoder* d, int mode, uint64_t n_paths, uint64_t first_path, uint64_t seed,
+                                uint32_t max_arcs, uint32_t max_tries, uint32_t* tries /* [n_paths], nullable */);
 
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
