@@ -49,6 +49,8 @@ SYMBOLS = [
     "carmel_hip_decode_pairs_sample",
     "carmel_hip_decode_pairs_kbest",
     "carmel_hip_decoder_generate",
+    "carmel_hip_decoder_best_paths",
+    "carmel_hip_decoder_best_paths_stats",
 ]
 
 
@@ -248,6 +250,8 @@ def _load():
     lib.carmel_hip_decode_pairs_sample.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
     lib.carmel_hip_decode_pairs_kbest.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp]
     lib.carmel_hip_decoder_generate.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, vp]
+    lib.carmel_hip_decoder_best_paths.argtypes = [vp, C.c_uint32, vp]
+    lib.carmel_hip_decoder_best_paths_stats.argtypes = [vp, vp, vp]
     for s in SYMBOLS:  # a prototype for every entry point: without one ctypes passes Python ints as C int (64-bit seeds
         if getattr(lib, s).argtypes is None:  # and bare handles would be truncated)
             raise ImportError("carmel_amd: no ctypes prototype for %s" % s)

@@ -227,6 +227,7 @@ int carmel_hip_decoder_set_weights(carmel_hip_decoder* d, const double* logw) {
   HIPCHK(hipSetDevice(d->device));
   d->logw.assign(logw, logw + d->n_arcs);
   d->gen_ready = false;  // (the generation tables hold the old weights' sums: the next carmel_hip_decoder_generate rebuilds them)
+  d->bp_ready = false;   // (and the next carmel_hip_decoder_best_paths its own)
   return d->upload_tables();  // (which arcs have weight zero may have changed)
 }
 

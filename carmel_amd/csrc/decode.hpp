@@ -1,6 +1,7 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
 // samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip,
-// decode_pairs_sample.hip and decode_pairs_kbest.hip; generation, decode_generate.hip, takes the handle and the path store) share: the prepared tables, the decoder
+// decode_pairs_sample.hip and decode_pairs_kbest.hip; generation, decode_generate.hip, and the whole machine's K best paths,
+// decode_best_paths.hip, take the handle and the path store) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built on
 // the host by build_decode_tables (decode_tables.hpp) and copied to the device by carmel_hip_decoder::upload_tables (decode.hip);
@@ -12,6 +13,7 @@
 #include <functional>
 #include <string>
 #include <vector>
+#include "decode_best_paths_tables.hpp"
 #include "decode_generate_tables.hpp"
 #include "decode_tables.hpp"
 #include "engine.hpp"
@@ -133,6 +135,17 @@ struct GenerateTables {
   const uint32_t* dst;
   const double* cum;
 };
+
+// The tables of the K best paths of the whole machine on the device (decode_best_paths_tables.hpp): the existing arcs by
+// destination, in arc-id order within one, and once more by source.
+struct BestPathsTables {
+  const uint32_t* in_off;   // [n_states + 1] -> the arcs into the state
+  const uint32_t* in_src;
+  const uint32_t* in_id;
+  const double* in_w;
+  const uint32_t* out_off;  // [n_states + 1] -> the arcs out of the state
+  const uint32_t* out_dst;
+};
 }  // namespace carmel_hip
 
 struct carmel_hip_decoder {
@@ -177,6 +190,16 @@ struct carmel_hip_decoder {
   carmel_hip::GenerateTables GJ, GC;  // joint: a list per state; conditional: a state's groups, a list per group
   DevBuf<uint32_t> gen_u32[7];
   DevBuf<double> gen_f64[2];
+  // the tables of the whole machine's K best paths (decode_best_paths_tables.hpp; carmel_hip_decoder_best_paths,
+  // decode_best_paths.hip): built and copied by the first call, dropped by carmel_hip_decoder_set_weights
+  bool bp_ready = false;
+  int64_t bp_cycle_arc = -1;  // an arc of weight above 1 on a cycle: the call refuses
+  uint64_t bp_n_in = 0;       // the arcs that exist
+  carmel_hip::BestPathsTables BP;
+  DevBuf<uint32_t> bp_u32[5];
+  DevBuf<double> bp_f64;
+  uint32_t bp_rounds = 0;     // the last successful call's statistics
+  uint64_t bp_selected = 0;
   double last_ms = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

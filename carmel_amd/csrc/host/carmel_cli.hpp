@@ -116,6 +116,8 @@ struct Options {
   // bounds the attempts a path may take
   long generate_paths = 0, generate_pairs = 0, generate_max_arcs = 1000, generate_tries = 256;
   bool have_generate_paths = false, have_generate_pairs = false, have_generate_max_arcs = false, have_generate_tries = false;
+  long best_paths = 0;  // --best-paths=N (carmel's -k N without -b / -i): the N best paths of the composed machine itself
+  bool have_best_paths = false;  // (carmel_hip_decoder_best_paths)
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };
@@ -184,6 +186,7 @@ int score_pairs(Job& j);
 void begin_training(Job& j);
 int decode_batch(const Options& o, carmel_host::Transducer& M, const std::string& text, int ws, bool quiet, int device);  // carmel_decode.cpp
 int generate_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
+int best_paths_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
 void log_lattice_stats(const carmel_hip_lattice_stats& ls, size_t n);      // carmel_em.cpp
 void train_em(Job& j, const Options& iteration_controls);
 int train_gibbs(Job& j);                                                   // carmel_gibbs.cpp

@@ -56,6 +56,7 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   std::vector<uint64_t> path_off, line_paths;
   std::vector<uint32_t> path;
   std::vector<const HArc*> arc_of;
+  std::vector<uint32_t> arc_src;  // the arc form of --best-paths=N: every arc's source state
   size_t n_0prob = 0;
   double n_prob = 0, prod_viterbi = 0;
   // --sum-paths (post_compose, carmel.cc:555-599): the lines whose sum of all paths is not zero, and the product of those sums
@@ -70,7 +71,7 @@ struct Batch {  // the lines of one call and what the four steps below make of t
   void posterior_counts(carmel_hip_decoder* d) const;
   void pair_counts(carmel_hip_decoder* d) const;
   void write_counts(std::vector<double>& count, const char* option, const std::string& file) const;
-  void format_path(uint64_t p, std::string& buf, bool pair_form = false) const;
+  void format_path(uint64_t p, std::string& buf, bool pair_form = false, bool arc_form = false) const;
   void print_paths(size_t kbest, bool quiet);
   void log_ppx(double n_pairs, double prod, size_t n_0) const;
   void report() const;
@@ -289,8 +290,9 @@ void Batch::write_counts(std::vector<double>& count, const char* option, const s
   if (!of) throw std::runtime_error(std::string(option) + ": cannot write " + file);
 }
 
-// one path of a line into buf, as path_print writes it; pair_form: the two lines of -@ whatever the switches say
-void Batch::format_path(uint64_t p, std::string& buf, bool pair_form) const {
+// one path of a line into buf, as path_print writes it; pair_form: the two lines of -@ whatever the switches say; arc_form:
+// path_print's default (fst.h:60-160), (src -> dst in : out / w) per arc, which needs arc_src
+void Batch::format_path(uint64_t p, std::string& buf, bool pair_form, bool arc_form) const {
   const bool fO = o.flags[(unsigned)'O'], fQ = o.flags[(unsigned)'Q'], fAT = o.flags[(unsigned)'@'] || pair_form, fW = o.flags[(unsigned)'W'],
              fE = o.flags[(unsigned)'E'];
   auto name = [&](bool output, uint32_t id) -> std::string {
@@ -311,6 +313,10 @@ void Batch::format_path(uint64_t p, std::string& buf, bool pair_form) const {
         sp();
         buf += M.in_syms.names[a.in];
       }
+    } else if (arc_form) {
+      sp();
+      buf += '(' + M.state_name(arc_src[path[k]]) + " -> " + M.state_name(a.dest) + ' ' + M.in_syms.names[a.in] + " : " +
+             M.out_syms.names[a.out] + " / " + format_weight(a.logw, ws) + ")";
     } else {
       const uint32_t id = fO ? a.out : a.in;
       if (!(fE && id == 0)) {
@@ -468,6 +474,55 @@ int generate_batch(const Options& o, Transducer& M, int ws, int device) {
       std::cout << buf;
       buf.clear();
     }
+  }
+  std::cout << buf << std::flush;
+  return 0;
+}
+
+// --best-paths=N (carmel's -k N without -b / -i: print_kbest(kPaths, result), carmel.cc:1380-1381, 379-397): the N best paths of
+// the composed machine itself (carmel_hip_decoder_best_paths, csrc/decode_best_paths.hip), best first, then print_kbest's fill
+// lines.  There is no line stream, and no transducer is written (carmel.cc:1485).  A path prints in the -I / -O forms (-Q -W -E
+// apply), as the pair it spells with -@, or else in path_print's arc form.
+int best_paths_batch(const Options& o, Transducer& M, int ws, int device) {
+  Batch b{o, M, ws};
+  std::vector<uint32_t> src, dst, in, out, group;
+  std::vector<double> logw;
+  M.flatten(src, dst, in, out, logw, group);
+  carmel_hip_decoder* d = 0;
+  hip_check(carmel_hip_decoder_create(&d, device, (uint32_t)M.states.size(), M.final_state, logw.size(), src.data(), dst.data(),
+                                      in.data(), out.data(), logw.data(), 0),
+            "carmel_hip_decoder_create");
+  struct Guard {
+    carmel_hip_decoder* d;
+    ~Guard() { carmel_hip_decoder_destroy(d); }
+  } guard{d};
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t n_paths = 0, n_path_arcs = 0;
+  hip_check(carmel_hip_decoder_best_paths(d, (uint32_t)o.best_paths, &n_paths), "carmel_hip_decoder_best_paths");
+  hip_check(carmel_hip_decoder_kbest_size(d, &n_paths, &n_path_arcs), "carmel_hip_decoder_kbest_size");
+  b.best.resize(std::max<uint64_t>(n_paths, 1));
+  b.path_off.resize(n_paths + 1);
+  b.path.resize(std::max<uint64_t>(n_path_arcs, 1));
+  hip_check(carmel_hip_decoder_get_kbest(d, b.best.data(), b.path_off.data(), b.path.data()), "carmel_hip_decoder_get_kbest");
+  if (timing_on()) {
+    double kms = 0;
+    uint32_t rounds = 0;
+    uint64_t selected = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    carmel_hip_decoder_best_paths_stats(d, &rounds, &selected);
+    std::cerr << "timing: best paths " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s (kernels "
+              << kms * 1e-3 << " s, " << rounds << " rounds, " << selected << " states selected)\n";
+  }
+  for (auto& st : M.states)
+    for (auto& a : st) b.arc_of.push_back(&a);
+  b.arc_src = src;
+  const bool fAT = o.flags[(unsigned)'@'], fW = o.flags[(unsigned)'W'];
+  const bool arc_form = !o.flags[(unsigned)'I'] && !o.flags[(unsigned)'O'] && !fAT;
+  std::string buf;
+  for (uint64_t p = 0; p < n_paths; ++p) b.format_path(p, buf, false, arc_form);
+  for (uint64_t f = n_paths; f < (uint64_t)o.best_paths; ++f) {  // print_kbest's fill lines
+    if (!(fW || fAT)) buf += '0';
+    buf += '\n';
   }
   std::cout << buf << std::flush;
   return 0;

@@ -44,13 +44,16 @@ static int print_help() {
                "one line each, with -I / -O (-Q -W -E) or two lines each with -@; --generate-pairs=N (carmel's -g N) prints N random "
                "input/output pairs, two lines each; --generate-max-arcs=L (carmel's -L, default 1000) bounds a path's arcs and "
                "--generate-tries=T (default 256) the attempts a path may take; "
+               "--best-paths=N (carmel's -k N without -b / -i, N <= 1024) prints the N best paths of the composed machine itself, best "
+               "first, one line each: with -I / -O (-Q -W -E), two lines each with -@, or else arc by arc (src -> dst in : out / w); "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
 
 // batch decoding (-b / -i with -k 1): what is not implemented is refused here, before any device call; true: decoding
 static bool validate_decoding(const Options& o, bool with_pairs) {
-  const bool decoding = o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0 || o.have_kbest || o.have_sample;
+  const bool decoding =
+      !o.have_best_paths && (o.flags[(unsigned)'b'] || o.flags[(unsigned)'i'] || o.kpaths != 0 || o.have_kbest || o.have_sample);
   if (o.have_posterior) {
     if (o.posterior_counts.empty()) throw UsageError("--posterior-counts=FILE needs a file name");
     if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i'])
@@ -101,12 +104,14 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
       if (o.kbest < 1 || o.kbest > 1024) throw UsageError("--kbest=N needs 1 <= N <= 1024");
       if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.kbest) throw UsageError("--kbest=N with -k m: m must be 1 or N");
     } else if (!o.have_pair_samples && !o.have_pair_kbest) {  // (--pair-samples=N, --pair-kbest=N: -k is absent, 1 or N, checked above)
+      if (o.kpaths > 1 && !o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i'])
+        throw UsageError("-k n without -b or -i (k-best paths of the whole cascade) is not implemented under that name; use --best-paths=n");
       if (o.kpaths > 1)
         throw UsageError("-k n with n > 1 (k-best paths) is not implemented; -k 1 with -b or -i is; use --kbest=n");
       if (o.kpaths < 1) throw UsageError("-b / -i without -k 1 (printing each line's composition) is not implemented");
     }
     if (!o.flags[(unsigned)'b'] && !o.flags[(unsigned)'i'])
-      throw UsageError("-k without -b or -i (k-best paths of the whole cascade) is not implemented");
+      throw UsageError("-k without -b or -i (k-best paths of the whole cascade) is not implemented under that name; use --best-paths=n");
     if (with_pairs) throw UsageError("-k with -t / --train-cascade / -S is not implemented");
     if (!o.flags[(unsigned)'I'] && !o.flags[(unsigned)'O'] && !o.flags[(unsigned)'@'])
       throw UsageError("-k without -I, -O or -@ (the arc path form: state names of a per-line composition) is not implemented");
@@ -115,6 +120,34 @@ static bool validate_decoding(const Options& o, bool with_pairs) {
   else if (o.sum)
     throw UsageError("--sum-paths applies to batch decoding (-b or -i with -k 1, --kbest=N or --sample-paths=N)");
   return decoding;
+}
+
+// the N best paths of the composed machine (--best-paths=N: carmel's -k N without -b / -i): usage errors name the option, before
+// any device call; true: listing them
+static bool validate_best_paths(const Options& o) {
+  if (!o.have_best_paths) return false;
+  if (o.best_paths < 1 || o.best_paths > 1024) throw UsageError("--best-paths=N needs 1 <= N <= 1024");
+  auto with = [&](bool on, const char* what) {
+    if (on) throw UsageError(std::string("--best-paths=N with ") + what + " is not implemented: it lists the paths of the composed machine, without lines or a corpus");
+  };
+  with(o.flags[(unsigned)'b'], "-b");
+  with(o.flags[(unsigned)'i'], "-i");
+  with(o.flags[(unsigned)'s'], "-s");
+  with(o.flags[(unsigned)'r'], "-r");
+  with(o.crp, "--crp");  // (which sets --train-cascade, which sets -t)
+  with(o.train_cascade, "--train-cascade");
+  with(o.flags[(unsigned)'t'], "-t");
+  with(o.flags[(unsigned)'S'], "-S");
+  with(o.flags[(unsigned)'F'], "-F");
+  with(o.have_pair_lines, "--pair-lines=FILE");
+  with(o.have_kbest, "--kbest=N");
+  with(o.have_sample, "--sample-paths=N");
+  with(o.have_generate_paths, "--generate-paths=N");
+  with(o.have_generate_pairs, "--generate-pairs=N");
+  with(o.have_generate_max_arcs, "--generate-max-arcs=L");
+  with(o.have_generate_tries, "--generate-tries=T");
+  if (o.kpaths != 0 && o.kpaths != 1 && o.kpaths != o.best_paths) throw UsageError("--best-paths=N with -k m: m must be 1 or N");
+  return true;
 }
 
 // generation (--generate-paths=N / --generate-pairs=N: carmel's -G / -g): usage errors name the switch, before any device call;
@@ -198,6 +231,7 @@ static int run(int argc, char** argv) {
   const bool scoring = !training && o.flags[(unsigned)'S'];  // carmel.cc:1134: -t overrides -S
   const bool with_pairs = training || scoring;
   if (o.flags[(unsigned)'h']) return print_help();
+  const bool listing = validate_best_paths(o);
   const bool generating = validate_generation(o);
   const bool decoding = validate_decoding(o, with_pairs);
   const std::string line_text = decoding ? read_line_stream(o) : std::string();
@@ -218,6 +252,7 @@ static int run(int argc, char** argv) {
   if (int rc = compose_members(j)) return rc;
   if (decoding) return decode_batch(o, *j.result, line_text, j.wstyle, j.quiet, o.gpu);
   if (generating) return generate_batch(o, *j.result, j.wstyle, o.gpu);
+  if (listing) return best_paths_batch(o, *j.result, j.wstyle, o.gpu);
   if (!with_pairs) return print_composition(j);
   read_corpus(j, corpus_text, /*weight_lines=*/!scoring);
   create_trainer(j);

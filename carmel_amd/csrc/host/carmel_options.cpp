@@ -142,6 +142,10 @@ Options parse_args(int argc, char** argv) {
         o.pair_kbest = std::atol(v.c_str());
         o.have_pair_kbest = true;
       }
+      else if (k == "best-paths") {  // carmel's -k N without -b / -i under another name: -k alone stays refused (carmel_main.cpp)
+        o.best_paths = std::atol(v.c_str());
+        o.have_best_paths = true;
+      }
       else if (k == "generate-paths") {  // carmel's -G N under another name (carmel.cc:1446-1458): -G itself stays refused, below
         o.generate_paths = std::atol(v.c_str());
         o.have_generate_paths = true;

@@ -22,7 +22,9 @@ const char* const kKeys[] = {
     "gibbs_chains", "gibbs_own_cap", "gibbs_workgroup", "gibbs_clk", "gibbs_reg", "gibbs_lane", "forest_sweep", "forest_ldswalk", "forest_multi",
     "forest_nohash", "forest_trace", "forest_exact_host", "forest_exact_clk", "forest_logdomain", "forest_gcol", "forest_gather",
     // batch decoding (decode.hip): "0" puts the trellis rows in global memory for any |Q|; the back-pointer budget of a chunk of lines
-    "decode_lds", "decode_chunk_bytes"};
+    "decode_lds", "decode_chunk_bytes",
+    // the K best paths of the whole machine (decode_best_paths.hip): states of more in-arcs than this are merged by a wavefront
+    "best_paths_wave_degree"};
 constexpr int kN = (int)(sizeof kKeys / sizeof kKeys[0]);
 const char* volatile g_val[kN];  // interned strings (a replaced value is not freed: a reader may still hold it)
 std::mutex g_mu;

@@ -15,6 +15,7 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     weights, kpaths = d.decode_pairs_kbest(lines, lines2, k)        # the k best alignments of every pair (csrc/decode_pairs_kbest.hip)
     paths = d.generate(n, mode="joint", seed=0)    # n random paths drawn from the machine itself (carmel -G n; csrc/decode_generate.hip)
     pairs = d.generate_pairs(n, seed=0)            # n random (input, output) strings (carmel -g n: mode "conditional")
+    kbest = d.best_paths(k)                        # the k best paths of the machine itself, best first (carmel -k n; csrc/decode_best_paths.hip)
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -217,6 +218,26 @@ class Decoder(object):
         isym, osym = self._keep[2], self._keep[3]
         return [([int(isym[a]) for a in path if isym[a]], [int(osym[a]) for a in path if osym[a]])
                 for _, path in self.generate(n, mode, seed, max_arcs, max_tries, first)]
+
+    def best_paths_raw(self, k):
+        """-> (logw, path_off, arcs): the min(k, number of paths) best paths of the whole machine from state 0 to the final state,
+        best first (carmel_hip_decoder_best_paths)"""
+        n = C.c_uint64()
+        check(lib.carmel_hip_decoder_best_paths(self._h, int(k), C.byref(n)), "carmel_hip_decoder_best_paths")
+        _, logw, path_off, arcs = self._last_paths(np.array([0, n.value], np.uint64))
+        return logw, path_off, arcs
+
+    def best_paths(self, k):
+        """-> [(reported ln weight, uint32 array of arc ids)]: the k best paths of the machine (carmel -k n; csrc/decode_best_paths.hip)"""
+        logw, path_off, arcs = self.best_paths_raw(k)
+        return [(float(logw[p]), arcs[int(path_off[p]):int(path_off[p + 1])].copy()) for p in range(len(logw))]
+
+    def best_paths_stats(self):
+        """-> (rounds, states_selected) of the last best_paths call"""
+        rounds, selected = C.c_uint32(), C.c_uint64()
+        check(lib.carmel_hip_decoder_best_paths_stats(self._h, C.byref(rounds), C.byref(selected)),
+              "carmel_hip_decoder_best_paths_stats")
+        return rounds.value, selected.value
 
     def posterior(self, lines, weights=None):
         """-> (sums, counts): sum(lines), and per arc its expected number of uses over the derivations of the lines (line l counts

@@ -756,6 +756,39 @@ int carmel_hip_decode_pairs_kbest(carmel_hip_decoder* d, uint32_t k, uint64_t n_
 int carmel_hip_decoder_generate(carmel_hip_decoder* d, int mode, uint64_t n_paths, uint64_t first_path, uint64_t seed,
                                 uint32_t max_arcs, uint32_t max_tries, uint32_t* tries /* [n_paths], nullable */);
 
+/* ---- the K best paths of the whole machine (carmel -k n without -b / -i; csrc/decode_best_paths.hip) ----
+ * Replaces: print_kbest(kPaths, result) on the composed result (carmel.cc:1380-1381, 379-397), WFST::visit_kbest (fst.h:791,
+ * kbest.h).  No lines are given; `side` plays no part; arc ids are those of carmel_hip_decoder_create.  The rule:
+ * Arcs.  Only arcs of log weight > -inf exist.  Symbols play no part: an *e*:*e* arc is an arc like any other.
+ * Paths.  A sequence of arcs from state 0 that ends in the final state; it may pass through the final state on the way.  The
+ * empty path exists if and only if the final state is state 0.  Two paths differ if their arc-id sequences differ.
+ * Value.  The arcs' logs added in path order from 0.0, ((0 + w1) + w2) + ...; the weight REPORTED is, as everywhere in the
+ * decoders, the arcs added from the END, w1 + (w2 + (... + (wn + 0))); the empty path reports 0.0.
+ * Lists.  Every state holds at most k entries (value f64, length u32, last arc u32, rank u16 of the predecessor in the last arc's
+ * source list).  The candidates of state q: for q = 0 the empty path (0.0, 0, no arc); for every arc a into q and every rank r of
+ * list(src a), (list(src a)[r].value + w(a), list(src a)[r].length + 1, a, r).  A k-way merge: every arc's candidates are taken
+ * in rank order, and among the arcs' current heads (and the empty path, which comes before anything of equal value) the next
+ * entry is the one of the greatest value, then the smallest length, then the lowest arc id.
+ * Rounds.  Round 0: list(0) = [empty path], every other list empty; round t + 1 computes every list from round t's (Jacobi); the
+ * result is the lists of the first round that equal the previous round's in all four fields.  Round t's lists are the k best
+ * walks of at most t arcs, so the result does not depend on scheduling, worklists or lane counts.
+ * Read-out.  Path r of list(final) is followed back through (arc, rank) to the empty path.
+ * Convergence.  More than k |Q| + 1 rounds: CARMEL_HIP_ERR_STATE ("did not converge").
+ * Weights above 1.  An existing arc of log weight > 0 whose source and destination lie on a common cycle (the same strongly
+ * connected component, or a self-loop): CARMEL_HIP_ERR_UNSUPPORTED, the message names the arc; such arcs off every cycle are legal.
+ * Deviations from the reference: its Eppstein search orders equal weights by its heap's pop order, here the order is total; cycles
+ * with weights above 1 are refused.
+ * CARMEL_HIP_ERR_ARG: a null argument, k outside 1 .. 1024, |Q| k >= 2^31.  An unreachable final state succeeds with 0 paths.
+ * The min(k, number of paths) paths are read, best first, with carmel_hip_decoder_kbest_size / carmel_hip_decoder_get_kbest; on
+ * failure the previous results stay.  May alternate with every other entry point on one handle, and sees the weights of
+ * carmel_hip_decoder_set_weights (its tables are built on the first call and dropped there); carmel_hip_decoder_last_ms covers
+ * its kernels.  Option "best_paths_wave_degree" (default 32): a state of more in-arcs is merged by a wavefront, not by a lane;
+ * the results are the same bytes. */
+int carmel_hip_decoder_best_paths(carmel_hip_decoder* d, uint32_t k, uint64_t* n_paths);
+/* the last successful carmel_hip_decoder_best_paths call: the rounds it ran and the sum over them of the number of states whose
+ * list was recomputed */
+int carmel_hip_decoder_best_paths_stats(carmel_hip_decoder* d, uint32_t* rounds, uint64_t* states_selected);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;
