@@ -1780,6 +1780,11 @@ __global__ void forest_mstep_kernel(double* rule_logw, const double* counts, dou
 bool forest_cols_exceed_lds(uint32_t max_nodes) { return forest_estimate_lds_bytes(max_nodes) > F_LDS_LIMIT; }
 size_t forest_estimate_lds_bytes(uint32_t max_nodes) { return (size_t)max_nodes * 64 * sizeof(double) * 2; }
 size_t forest_estimate_ext_lds_bytes(uint32_t max_nodes) { return (size_t)max_nodes * 64 * 24; }
+FEstepKind forest_estep_kind(uint32_t max_nodes) {
+  if (forest_cols_exceed_lds(max_nodes)) return F_ESTEP_GCOL;
+  return forest_estimate_ext_lds_bytes(max_nodes) <= F_LDS_LIMIT ? F_ESTEP_EXT : F_ESTEP_LOG;
+}
+const char* forest_estep_kind_name(FEstepKind k) { return k == F_ESTEP_EXT ? "ext" : k == F_ESTEP_LOG ? "log" : "gcol"; }
 size_t forest_gibbs_lds_bytes(bool gcol, uint32_t ins_rows, uint32_t own_cap, uint32_t stack_lds) {
   return (gcol ? 0 : (size_t)ins_rows * 64 * 8) + (size_t)own_cap * 64 * 4 + (size_t)stack_lds * 64 * 4;
 }

@@ -108,6 +108,11 @@ struct FMultiArgs {
 bool forest_cols_exceed_lds(uint32_t max_nodes);
 size_t forest_estimate_lds_bytes(uint32_t max_nodes);      // forest_estimate_kernel<false>: the two columns
 size_t forest_estimate_ext_lds_bytes(uint32_t max_nodes);  // forest_estimate_ext_kernel: 24 bytes a node and lane
+// the E-step kernel of a launch class, by its largest forest: mantissa / exponent arithmetic where 24 bytes a node and lane fit
+// LDS, else the log domain with its two columns in LDS, else the log domain with the columns in global memory
+enum FEstepKind { F_ESTEP_EXT, F_ESTEP_LOG, F_ESTEP_GCOL };
+FEstepKind forest_estep_kind(uint32_t max_nodes);
+const char* forest_estep_kind_name(FEstepKind k);  // "ext", "log", "gcol"
 // forest_gibbs_kernel: the inside column (unless in global memory), own_cap hash slots and stack_lds stack words a lane
 size_t forest_gibbs_lds_bytes(bool gcol, uint32_t ins_rows, uint32_t own_cap, uint32_t stack_lds);
 // forest_sample_kernel: the column (EXT: 12 bytes a node, else 8) and the stack ...

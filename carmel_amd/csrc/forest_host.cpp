@@ -368,6 +368,10 @@ int carmel_hip_forests_create(carmel_hip_forests** out, int device, uint64_t n_f
       F->classes.push_back(c);
       i = j;
     }
+    if (lib_opt("timing"))
+      for (const auto& c : F->classes)
+        fprintf(stderr, "timing:   forest class first=%u count=%u max_nodes=%u estep=%s\n", c.first, c.count, c.max_nodes,
+                forest_estep_kind_name(forest_estep_kind(c.max_nodes)));
   }
   {  // classes too large for LDS keep their columns in global memory
     uint64_t tot = 0;
@@ -634,14 +638,15 @@ int carmel_hip_forests_estimate(carmel_hip_forests* F, double prior_count, doubl
   for (size_t ci = 0; ci < F->classes.size(); ++ci) {
     const auto& c = F->classes[ci];
     A.first_group = c.first;
-    if (forest_cols_exceed_lds(c.max_nodes)) {
+    const FEstepKind kind = forest_estep_kind(c.max_nodes);
+    if (kind == F_ESTEP_GCOL) {
       A.gcol = F->gcol.p + F->gcol_off[ci];
       A.gcol_stride = (uint64_t)2 * c.max_nodes * 64;
-      HIPCHK(launch_forest_estimate(A, true, c.count, c.max_nodes, class_stream(F, s, ci)));
-    } else if (forest_estimate_ext_lds_bytes(c.max_nodes) <= F_LDS_LIMIT)
+    }
+    if (kind == F_ESTEP_EXT)
       HIPCHK(launch_forest_estimate_ext(A, c.count, c.max_nodes, class_stream(F, s, ci)));
     else
-      HIPCHK(launch_forest_estimate(A, false, c.count, c.max_nodes, class_stream(F, s, ci)));
+      HIPCHK(launch_forest_estimate(A, kind == F_ESTEP_GCOL, c.count, c.max_nodes, class_stream(F, s, ci)));
   }
   HIPCHK(join_side(F, s));
   ReduceArgs R;
