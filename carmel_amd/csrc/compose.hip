@@ -22,6 +22,7 @@
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <memory>
 #include <type_traits>
 #include <cstring>
@@ -377,10 +378,13 @@ int carmel_hip_compose(carmel_hip_composition** out, int device, uint32_t a_stat
     int rc = rebuild_table(cap, 1);
     if (rc) return rc;
   }
-  uint32_t lo = 0, hi = 1;
+  uint32_t lo = 0, hi = 1, max_frontier = 0;
   uint64_t n_arcs = 0;
+  std::string reinserted;  // the states each table rebuild put back, for the timing line
+  uint32_t n_rebuilds = 0;
   while (lo < hi) {
     const uint32_t nf = hi - lo;
+    max_frontier = std::max(max_frontier, nf);
     if (counts.n < nf) HIPCHK(counts.alloc((size_t)nf * 2));
     if (level_off.n < nf) HIPCHK(level_off.alloc((size_t)nf * 2));
     G.lo = lo;
@@ -415,6 +419,7 @@ int carmel_hip_compose(carmel_hip_composition** out, int device, uint32_t a_stat
     if (2 * max_states > cap) {
       int rc = rebuild_table(2 * max_states, n_states);
       if (rc) return rc;
+      reinserted += (n_rebuilds++ ? "," : "") + std::to_string(n_states);
     }
     G.st_qa = C->st_qa.p;
     G.st_qb = C->st_qb.p;
@@ -443,6 +448,9 @@ int carmel_hip_compose(carmel_hip_composition** out, int device, uint32_t a_stat
   C->n_states = n_states;
   C->n_arcs = n_arcs;
   C->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (carmel_hip::lib_opt("timing"))  // what the run went through: the tests hold it to the sequential construction's own account
+    fprintf(stderr, "timing: compose levels=%u max_frontier=%u rebuilds=%u reinserted=%s state_capacity=%zu table_capacity=%llu\n",
+            C->levels, max_frontier, n_rebuilds, n_rebuilds ? reinserted.c_str() : "-", C->st_qa.n, (unsigned long long)cap);
   *out = C.release();
   return CARMEL_HIP_OK;
 }
