@@ -1,7 +1,7 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
 // samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip,
 // decode_pairs_sample.hip and decode_pairs_kbest.hip; generation, decode_generate.hip, and the whole machine's K best paths,
-// decode_best_paths.hip, take the handle and the path store) share: the prepared tables, the decoder
+// decode_best_paths.hip, take the handle and the path store; its pruning, decode_prune.hip, the handle) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built on
 // the host by build_decode_tables (decode_tables.hpp) and copied to the device by carmel_hip_decoder::upload_tables (decode.hip);
@@ -200,6 +200,17 @@ struct carmel_hip_decoder {
   DevBuf<double> bp_f64;
   uint32_t bp_rounds = 0;     // the last successful call's statistics
   uint64_t bp_selected = 0;
+  // pruning by best-path weight (carmel_hip_decoder_prune, decode_prune.hip): the tables of the forward and the backward pass for
+  // one arc threshold, built and copied by the first call with it, dropped by carmel_hip_decoder_set_weights; the last successful
+  // call's distances and rounds
+  bool pr_ready = false, pr_have = false;
+  double pr_min_arc_logw = 0;
+  int64_t pr_cycle_arc = -1;
+  carmel_hip::BestPathsTables PR[2];  // forward, backward
+  DevBuf<uint32_t> pr_u32[10], pr_dst;  // pr_dst: every arc's destination, beside a_src
+  DevBuf<double> pr_f64[2];
+  std::vector<double> pr_fwd, pr_bwd;
+  uint32_t pr_rounds[2] = {0, 0};
   double last_ms = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

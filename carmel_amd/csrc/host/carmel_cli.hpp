@@ -118,6 +118,11 @@ struct Options {
   bool have_generate_paths = false, have_generate_pairs = false, have_generate_max_arcs = false, have_generate_tries = false;
   long best_paths = 0;  // --best-paths=N (carmel's -k N without -b / -i): the N best paths of the composed machine itself
   bool have_best_paths = false;  // (carmel_hip_decoder_best_paths)
+  // --prune-paths=W (carmel's -w w), --prune-states=N (-z n), --prune-arcs=W (-p w): the composed machine is pruned by best-path
+  // weight before it is printed (carmel_hip_decoder_prune): ln of the ratio (below 1: 1), the state cap, ln of the arc threshold
+  double prune_log_ratio = std::numeric_limits<double>::infinity(), prune_min_arc_logw = -std::numeric_limits<double>::infinity();
+  long prune_states = 0;
+  bool have_prune_paths = false, have_prune_states = false, have_prune_arcs = false;
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };
@@ -187,6 +192,7 @@ void begin_training(Job& j);
 int decode_batch(const Options& o, carmel_host::Transducer& M, const std::string& text, int ws, bool quiet, int device);  // carmel_decode.cpp
 int generate_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
 int best_paths_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
+int prune_composition(const Options& o, carmel_host::Transducer& M, bool quiet, int device);
 void log_lattice_stats(const carmel_hip_lattice_stats& ls, size_t n);      // carmel_em.cpp
 void train_em(Job& j, const Options& iteration_controls);
 int train_gibbs(Job& j);                                                   // carmel_gibbs.cpp

@@ -527,3 +527,43 @@ int best_paths_batch(const Options& o, Transducer& M, int ws, int device) {
   std::cout << buf << std::flush;
   return 0;
 }
+
+// --prune-paths=W / --prune-states=N / --prune-arcs=W (carmel's -w / -z / -p: carmel_main::prune in shrink, carmel.cc:633-636,
+// 674-677): the composed and reduced machine is flattened, carmel_hip_decoder_prune (csrc/decode_prune.hip) marks what stays, and
+// Transducer::keep applies the masks.  A state cap can leave dead ends: unless -d is given the machine is reduced once more (the
+// reference leaves them in place).  Without -q the shrink_monitor note ` prune-> states/arcs` goes to stderr if anything went.
+int prune_composition(const Options& o, Transducer& M, bool quiet, int device) {
+  if (M.states.empty()) return 0;  // (nothing to prune)
+  std::vector<uint32_t> src, dst, in, out, group;
+  std::vector<double> logw;
+  M.flatten(src, dst, in, out, logw, group);
+  carmel_hip_decoder* d = 0;
+  hip_check(carmel_hip_decoder_create(&d, device, (uint32_t)M.states.size(), M.final_state, logw.size(), src.data(), dst.data(),
+                                      in.data(), out.data(), logw.data(), 0),
+            "carmel_hip_decoder_create");
+  struct Guard {
+    carmel_hip_decoder* d;
+    ~Guard() { carmel_hip_decoder_destroy(d); }
+  } guard{d};
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint8_t> state_keep(M.states.size()), arc_keep(std::max<size_t>(logw.size(), 1));
+  const uint32_t cap = o.have_prune_states ? (uint32_t)std::min<long>(o.prune_states, 0xffffffffl) : 0xffffffffu;
+  uint64_t n_states = 0, n_arcs = 0;
+  hip_check(carmel_hip_decoder_prune(d, o.prune_log_ratio, cap, o.prune_min_arc_logw, state_keep.data(), arc_keep.data(), &n_states,
+                                     &n_arcs),
+            "carmel_hip_decoder_prune");
+  if (timing_on()) {
+    double kms = 0;
+    uint32_t fr = 0, br = 0;
+    carmel_hip_decoder_last_ms(d, &kms);
+    carmel_hip_decoder_prune_stats(d, &fr, &br);
+    std::cerr << "timing: prune " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s (kernels "
+              << kms * 1e-3 << " s, " << fr << " F rounds, " << br << " R rounds)\n";
+  }
+  const size_t st = M.states.size(), ar = M.num_arcs();
+  M.keep(state_keep, arc_keep);
+  if (!o.flags[(unsigned)'d']) M.prune_useless();
+  if (!quiet && (M.states.size() != st || M.num_arcs() != ar))
+    std::cerr << "\t(" << st << " states / " << ar << " arcs prune-> " << M.states.size() << "/" << M.num_arcs() << ")" << std::endl;
+  return 0;
+}

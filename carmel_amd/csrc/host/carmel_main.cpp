@@ -46,6 +46,9 @@ static int print_help() {
                "--generate-tries=T (default 256) the attempts a path may take; "
                "--best-paths=N (carmel's -k N without -b / -i, N <= 1024) prints the N best paths of the composed machine itself, best "
                "first, one line each: with -I / -O (-Q -W -E), two lines each with -@, or else arc by arc (src -> dst in : out / w); "
+               "pruning the composed machine before it is printed (also with -c or -F): --prune-paths=W (carmel's -w W) keeps the states "
+               "and arcs on a path at most W times worse than the best path, --prune-states=N (carmel's -z N) at most N states, those "
+               "of the best paths through them, --prune-arcs=W (carmel's -p W) no arc of a weight below W; "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -150,6 +153,27 @@ static bool validate_best_paths(const Options& o) {
   return true;
 }
 
+// pruning (--prune-paths=W / --prune-states=N / --prune-arcs=W: carmel's -w / -z / -p) applies to the compose-and-print path only:
+// usage errors name the option, before any device call; true: pruning
+static bool validate_pruning(const Options& o) {
+  if (!o.have_prune_paths && !o.have_prune_states && !o.have_prune_arcs) return false;
+  const char* sw = o.have_prune_paths ? "--prune-paths=W" : o.have_prune_states ? "--prune-states=N" : "--prune-arcs=W";
+  auto with = [&](bool on, const char* what) {
+    if (on) throw UsageError(std::string(sw) + " with " + what + " is not implemented: it prunes the composed machine that is printed, without lines or a corpus");
+  };
+  with(o.flags[(unsigned)'b'], "-b");
+  with(o.flags[(unsigned)'i'], "-i");
+  with(o.crp, "--crp");  // (which sets --train-cascade, which sets -t)
+  with(o.train_cascade, "--train-cascade");
+  with(o.flags[(unsigned)'t'], "-t");
+  with(o.flags[(unsigned)'S'], "-S");
+  with(o.have_best_paths, "--best-paths=N");
+  with(o.have_generate_paths, "--generate-paths=N");
+  with(o.have_generate_pairs, "--generate-pairs=N");
+  with(o.kpaths != 0, "-k");
+  return true;
+}
+
 // generation (--generate-paths=N / --generate-pairs=N: carmel's -G / -g): usage errors name the switch, before any device call;
 // true: generating
 static bool validate_generation(const Options& o) {
@@ -213,13 +237,23 @@ static int weight_style(const Options& o) {
   return wstyle;
 }
 
-static int print_composition(const Job& j) {  // plain `carmel a b ...`: print the (reduced) composition — no GPU involved
+// plain `carmel a b ...`: print the (reduced) composition — no GPU involved; after pruning, to the -F file if one is named
+static int print_composition(const Job& j, bool to_file = false) {
   const Options& o = j.o;
+  std::ofstream of;
+  if (to_file) {
+    of.open(o.out_file.c_str());
+    if (!of) {
+      std::cerr << "Could not create file " << o.out_file << ".\n";
+      return -8;
+    }
+  }
+  std::ostream& os = to_file ? static_cast<std::ostream&>(of) : std::cout;
   if (o.flags[(unsigned)'c'])
-    std::cout << "Number of states in result: " << j.result->states.size() << "\nNumber of arcs in result: "
-              << j.result->num_arcs() << "\n";
+    os << "Number of states in result: " << j.result->states.size() << "\nNumber of arcs in result: "
+       << j.result->num_arcs() << "\n";
   else
-    std::cout << j.result->to_text(o.flags[(unsigned)'J'], o.flags[(unsigned)'H'], j.wstyle);
+    os << j.result->to_text(o.flags[(unsigned)'J'], o.flags[(unsigned)'H'], j.wstyle);
   return 0;
 }
 
@@ -231,6 +265,7 @@ static int run(int argc, char** argv) {
   const bool scoring = !training && o.flags[(unsigned)'S'];  // carmel.cc:1134: -t overrides -S
   const bool with_pairs = training || scoring;
   if (o.flags[(unsigned)'h']) return print_help();
+  const bool pruning = validate_pruning(o);
   const bool listing = validate_best_paths(o);
   const bool generating = validate_generation(o);
   const bool decoding = validate_decoding(o, with_pairs);
@@ -253,6 +288,10 @@ static int run(int argc, char** argv) {
   if (decoding) return decode_batch(o, *j.result, line_text, j.wstyle, j.quiet, o.gpu);
   if (generating) return generate_batch(o, *j.result, j.wstyle, o.gpu);
   if (listing) return best_paths_batch(o, *j.result, j.wstyle, o.gpu);
+  if (pruning) {
+    if (int rc = prune_composition(o, *j.result, j.quiet, o.gpu)) return rc;
+    return print_composition(j, !o.out_file.empty());
+  }
   if (!with_pairs) return print_composition(j);
   read_corpus(j, corpus_text, /*weight_lines=*/!scoring);
   create_trainer(j);

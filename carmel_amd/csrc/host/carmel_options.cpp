@@ -146,6 +146,23 @@ Options parse_args(int argc, char** argv) {
         o.best_paths = std::atol(v.c_str());
         o.have_best_paths = true;
       }
+      else if (k == "prune-paths") {  // carmel's -w w under another name (carmel.cc:951-952): -w itself stays refused, below
+        if (v.empty() || !parse_weight_token(v, o.prune_log_ratio) || o.prune_log_ratio != o.prune_log_ratio)
+          throw UsageError("--prune-paths=W needs a weight (the ratio to the best path's weight: carmel's -w W)");
+        if (!(o.prune_log_ratio >= 0.0)) o.prune_log_ratio = 0.0;  // a ratio below 1 becomes 1
+        o.have_prune_paths = true;
+      }
+      else if (k == "prune-states") {  // carmel's -z n (carmel.cc:955)
+        char* end = nullptr;
+        o.prune_states = std::strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || o.prune_states < 1) throw UsageError("--prune-states=N needs a number N >= 1 (carmel's -z N)");
+        o.have_prune_states = true;
+      }
+      else if (k == "prune-arcs") {  // carmel's -p w (carmel.cc:979)
+        if (v.empty() || !parse_weight_token(v, o.prune_min_arc_logw) || o.prune_min_arc_logw != o.prune_min_arc_logw)
+          throw UsageError("--prune-arcs=W needs a weight (arcs below it are discarded: carmel's -p W)");
+        o.have_prune_arcs = true;
+      }
       else if (k == "generate-paths") {  // carmel's -G N under another name (carmel.cc:1446-1458): -G itself stays refused, below
         o.generate_paths = std::atol(v.c_str());
         o.have_generate_paths = true;
@@ -271,6 +288,9 @@ Options parse_args(int argc, char** argv) {
           case 'g': throw UsageError("switch -g n is not implemented under that name; use --generate-pairs=n");
           case 'G': throw UsageError("switch -G n is not implemented under that name; use --generate-paths=n");
           case 'L': throw UsageError("switch -L n is not implemented under that name; use --generate-max-arcs=n");
+          case 'w': throw UsageError("switch -w w is not implemented under that name; use --prune-paths=w");
+          case 'z': throw UsageError("switch -z n is not implemented under that name; use --prune-states=n");
+          case 'p': throw UsageError("switch -p w is not implemented under that name; use --prune-arcs=w");
           default:
             // switches without a value that this front end implements; everything else carmel knows (k-best, generation,
             // projection, pruning, OpenFst, ...) is outside the training path

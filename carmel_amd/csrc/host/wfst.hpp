@@ -250,6 +250,41 @@ class Transducer {
     return true;
   }
 
+  // keep the states and the arcs that the masks name (arc ids in flatten's order; an arc also needs both its states), renumbering
+  // the states in order and keeping their names, as prune_useless does; the machine is cleared when nothing is kept, that is when
+  // state 0 or the final state goes.  -> false: cleared
+  bool keep(const std::vector<uint8_t>& state_keep, const std::vector<uint8_t>& arc_keep) {
+    const uint32_t n = (uint32_t)states.size();
+    if (!n || !state_keep[0] || !state_keep[final_state]) {
+      states.clear();
+      return false;
+    }
+    std::vector<uint32_t> remap(n, kNoGroup);
+    uint32_t k = 0;
+    for (uint32_t s = 0; s < n; ++s)
+      if (state_keep[s]) remap[s] = k++;
+    std::vector<std::vector<HArc> > ns(k);
+    std::vector<std::string> nn;
+    size_t id = 0;
+    for (uint32_t s = 0; s < n; ++s) {
+      for (auto a : states[s]) {
+        const size_t mine = id++;
+        if (remap[s] == kNoGroup || remap[a.dest] == kNoGroup || !arc_keep[mine]) continue;
+        a.dest = remap[a.dest];
+        ns[remap[s]].push_back(a);
+      }
+      if (remap[s] != kNoGroup && named && s < state_names.size()) nn.push_back(state_names[s]);
+    }
+    states.swap(ns);
+    final_state = remap[final_state];
+    if (named) {
+      state_names.swap(nn);
+      name_ids_.clear();
+      for (uint32_t i = 0; i < state_names.size(); ++i) name_ids_[state_names[i]] = i;
+    }
+    return true;
+  }
+
   // ---- writer (wfstio.cc:594-625) ----
   std::string to_text(bool full /*-J*/, bool arc_per_line /*-H*/, int wstyle, bool include_zero = false) const {
     std::string o = state_name(final_state);

@@ -16,6 +16,8 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     paths = d.generate(n, mode="joint", seed=0)    # n random paths drawn from the machine itself (carmel -G n; csrc/decode_generate.hip)
     pairs = d.generate_pairs(n, seed=0)            # n random (input, output) strings (carmel -g n: mode "conditional")
     kbest = d.best_paths(k)                        # the k best paths of the machine itself, best first (carmel -k n; csrc/decode_best_paths.hip)
+    state_keep, arc_keep = d.prune(log_ratio, max_states, min_arc_logw)   # what stays of the machine (carmel -w / -z / -p; csrc/decode_prune.hip)
+    F, R = d.prune_distances()                     # the best distance from state 0 to every state and from every state to the final one
     d.set_weights(logw); d.close()
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
@@ -62,7 +64,7 @@ def _pack(lines):
 
 class Decoder(object):
     def __init__(self, wfst, side=0, device=0):
-        self.n_arcs = wfst.n_arcs
+        self.n_arcs, self.n_states = wfst.n_arcs, wfst.n_states
         self._h = C.c_void_p()
         self._keep = [u32(wfst.src), u32(wfst.dst), u32(wfst.isym), u32(wfst.osym)]
         check(lib.carmel_hip_decoder_create(C.byref(self._h), device, wfst.n_states, wfst.final, wfst.n_arcs,
@@ -238,6 +240,33 @@ class Decoder(object):
         check(lib.carmel_hip_decoder_best_paths_stats(self._h, C.byref(rounds), C.byref(selected)),
               "carmel_hip_decoder_best_paths_stats")
         return rounds.value, selected.value
+
+    def prune(self, log_ratio=np.inf, max_states=None, min_arc_logw=-np.inf):
+        """-> (state_keep, arc_keep), bool arrays: the states and arcs that lie on a path from state 0 to the final state whose
+        weight is within log_ratio of the best path's, at most max_states states (those of the best paths through them), no arc of
+        log weight below min_arc_logw (carmel_hip_decoder_prune; include/carmel_hip.h has the rule)"""
+        state_keep = np.zeros(self.n_states, np.uint8)
+        arc_keep = np.zeros(max(self.n_arcs, 1), np.uint8)
+        ns, na = C.c_uint64(), C.c_uint64()
+        cap = 0xFFFFFFFF if max_states is None else int(max_states)
+        check(lib.carmel_hip_decoder_prune(self._h, float(log_ratio), cap, float(min_arc_logw), ptr(state_keep), ptr(arc_keep),
+                                           C.byref(ns), C.byref(na)), "carmel_hip_decoder_prune")
+        arc_keep = arc_keep[:self.n_arcs]
+        assert ns.value == int(state_keep.sum()) and na.value == int(arc_keep.sum())
+        return state_keep.astype(bool), arc_keep.astype(bool)
+
+    def prune_distances(self):
+        """-> (F, R) of the last prune call: per state the best value of a path from state 0 to it and from it to the final state
+        (-inf: none)"""
+        fwd, bwd = np.empty(self.n_states), np.empty(self.n_states)
+        check(lib.carmel_hip_decoder_prune_distances(self._h, ptr(fwd), ptr(bwd)), "carmel_hip_decoder_prune_distances")
+        return fwd, bwd
+
+    def prune_stats(self):
+        """-> (forward rounds, backward rounds) of the last prune call"""
+        f, b = C.c_uint32(), C.c_uint32()
+        check(lib.carmel_hip_decoder_prune_stats(self._h, C.byref(f), C.byref(b)), "carmel_hip_decoder_prune_stats")
+        return f.value, b.value
 
     def posterior(self, lines, weights=None):
         """-> (sums, counts): sum(lines), and per arc its expected number of uses over the derivations of the lines (line l counts

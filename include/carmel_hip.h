@@ -789,6 +789,48 @@ int carmel_hip_decoder_best_paths(carmel_hip_decoder* d, uint32_t k, uint64_t* n
  * list was recomputed */
 int carmel_hip_decoder_best_paths_stats(carmel_hip_decoder* d, uint32_t* rounds, uint64_t* states_selected);
 
+/* ---- pruning the whole machine by best-path weight (carmel -w w, -z n, -p w; csrc/decode_prune.hip) ----
+ * Replaces: WFST::prunePaths (fst.cc:382-466) and WFST::pruneArcs (fst.cc:20-22) on the composed result (carmel.cc:533, 633-636).
+ * No lines are given; `side` plays no part; arc and state ids are those of carmel_hip_decoder_create.  The call marks what stays
+ * and changes nothing in the handle's machine.  The rule:
+ * Inputs.  log_ratio >= 0, or +inf for no ratio test; max_states >= 1, or UINT32_MAX for no cap; min_arc_logw, or -inf for no arc
+ * threshold.
+ * Arcs.  An arc exists if its log weight is > -inf and >= min_arc_logw.  Symbols play no part.
+ * Forward distance F[q].  Exactly list(q) of carmel_hip_decoder_best_paths at K = 1 on the existing arcs: an entry is (value,
+ * length, last arc); the value is the arcs' logs added in path order from 0.0; ties go to the smaller length, then to the lower
+ * arc id; the empty path at state 0 comes first; Jacobi rounds to the first fixed point; an unreachable state has -inf.
+ * Backward distance R[q].  The same computation on the reversed machine, started at the final state: every existing arc is turned
+ * round.  The value is then w1 + (w2 + (... + (wn + 0))), because floating-point addition commutes: the decoders' "reported"
+ * fold.  The tie order is the same.
+ * Through values.  T(q) = F[q] + R[q]; T(a) = (F[src a] + w(a)) + R[dst a]; either is -inf when a term is -inf.
+ * Limit.  limit = F[final] - log_ratio; it is -inf when log_ratio = +inf.
+ * Best path P*.  The path the K = 1 back-pointers give from the final state.  Its arcs and states pass the ratio test by
+ * definition: rounding may put T(a) of one of P*'s own arcs an ulp below F[final], and a ratio of 1 must keep the best path.
+ * (The reference has this hazard in float and asserts it away only in debug builds.)
+ * State cap.  The states are ordered by T(q) descending, then by state id ascending; states of rank >= max_states are removed.
+ * P* is not exempt from the cap.
+ * State kept iff its rank is < max_states and (T(q) >= limit or q is on P*).
+ * Arc kept iff it exists, its source and destination are kept, and (T(a) >= limit or the arc is on P*).
+ * No path or lost endpoint.  F[final] = -inf, or state 0 or the final state not kept: nothing is kept; the call succeeds with
+ * counts 0.
+ * Refused.  An existing arc of log weight > 0 on a cycle: CARMEL_HIP_ERR_UNSUPPORTED, the same arc and the same message form as
+ * carmel_hip_decoder_best_paths.
+ * Deviations from the reference: it has no P* exemption; the order for the cap is total, where it uses an unstable std::sort;
+ * arcs of weight 0 are never kept; positive-weight cycles are refused.
+ * state_keep and arc_keep receive a byte of 0 or 1 per state and per arc; the counts may be null.  More than |Q| + 1 rounds of
+ * either pass: CARMEL_HIP_ERR_STATE.  CARMEL_HIP_ERR_ARG: a null handle or mask, log_ratio NaN or < 0, max_states 0, min_arc_logw
+ * NaN.  On failure the handle's earlier results stay.  May alternate with every other entry point on one handle, and sees the
+ * weights of carmel_hip_decoder_set_weights (its tables are built on the first call and dropped there);
+ * carmel_hip_decoder_last_ms covers its kernels.  Option "best_paths_wave_degree" as for carmel_hip_decoder_best_paths. */
+int carmel_hip_decoder_prune(carmel_hip_decoder* d, double log_ratio, uint32_t max_states, double min_arc_logw,
+                             uint8_t* state_keep /* [n_states] */, uint8_t* arc_keep /* [n_arcs] */,
+                             uint64_t* n_states_kept, uint64_t* n_arcs_kept);
+/* the last successful prune call's F and R, n_states entries each; either may be null.  CARMEL_HIP_ERR_STATE before any
+ * successful prune call. */
+int carmel_hip_decoder_prune_distances(carmel_hip_decoder* d, double* fwd, double* bwd);
+/* the last successful prune call: the rounds of the forward and of the backward pass */
+int carmel_hip_decoder_prune_stats(carmel_hip_decoder* d, uint32_t* fwd_rounds, uint32_t* bwd_rounds);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;
