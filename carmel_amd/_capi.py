@@ -54,6 +54,7 @@ SYMBOLS = [
     "carmel_hip_decoder_prune",
     "carmel_hip_decoder_prune_distances",
     "carmel_hip_decoder_prune_stats",
+    "carmel_hip_consolidate",
 ]
 
 
@@ -258,6 +259,7 @@ def _load():
     lib.carmel_hip_decoder_prune.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, vp, vp, vp, vp]
     lib.carmel_hip_decoder_prune_distances.argtypes = [vp, vp, vp]
     lib.carmel_hip_decoder_prune_stats.argtypes = [vp, vp, vp]
+    lib.carmel_hip_consolidate.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     for s in SYMBOLS:  # a prototype for every entry point: without one ctypes passes Python ints as C int (64-bit seeds
         if getattr(lib, s).argtypes is None:  # and bare handles would be truncated)
             raise ImportError("carmel_amd: no ctypes prototype for %s" % s)

@@ -123,6 +123,10 @@ struct Options {
   double prune_log_ratio = std::numeric_limits<double>::infinity(), prune_min_arc_logw = -std::numeric_limits<double>::infinity();
   long prune_states = 0;
   bool have_prune_paths = false, have_prune_states = false, have_prune_arcs = false;
+  // -C (carmel's own switch: WFST::consolidateArcs): arcs of the composed machine with the same source, destination, input and
+  // output become one arc of their summed weight (carmel_hip_consolidate); --consolidate-max keeps the largest weight instead,
+  // --consolidate-unclamped lets a sum exceed 1
+  bool consolidate_max = false, consolidate_unclamped = false;
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };
@@ -193,6 +197,7 @@ int decode_batch(const Options& o, carmel_host::Transducer& M, const std::string
 int generate_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
 int best_paths_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
 int prune_composition(const Options& o, carmel_host::Transducer& M, bool quiet, int device);
+int consolidate_composition(const Options& o, carmel_host::Transducer& M, bool quiet, int device);
 void log_lattice_stats(const carmel_hip_lattice_stats& ls, size_t n);      // carmel_em.cpp
 void train_em(Job& j, const Options& iteration_controls);
 int train_gibbs(Job& j);                                                   // carmel_gibbs.cpp

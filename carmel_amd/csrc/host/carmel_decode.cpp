@@ -567,3 +567,35 @@ int prune_composition(const Options& o, Transducer& M, bool quiet, int device) {
     std::cerr << "\t(" << st << " states / " << ar << " arcs prune-> " << M.states.size() << "/" << M.num_arcs() << ")" << std::endl;
   return 0;
 }
+
+// -C with --consolidate-max / --consolidate-unclamped (carmel_main::minimize, carmel.cc:638-642: consolidate, then reduce, before
+// any pruning): the composed machine is flattened, carmel_hip_consolidate (csrc/consolidate.hip) names every segment's first arc
+// and its weight, and Transducer::consolidate keeps those.  A segment of arcs of weight zero disappears, which can leave a dead
+// end: unless -d is given the machine is reduced once more.  Only the final result of a chain of transducers is consolidated.
+// Without -q the shrink_monitor note ` consolidate-> states/arcs` goes to stderr if anything went.
+int consolidate_composition(const Options& o, Transducer& M, bool quiet, int device) {
+  if (M.states.empty()) return 0;  // (nothing to consolidate)
+  std::vector<uint32_t> src, dst, in, out, group;
+  std::vector<double> logw;
+  M.flatten(src, dst, in, out, logw, group);
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t n = logw.size();
+  std::vector<uint32_t> arc_map(std::max<size_t>(n, 1)), kept_id(std::max<size_t>(n, 1));
+  std::vector<double> kept_logw(std::max<size_t>(n, 1));
+  uint64_t n_kept = 0;
+  double kms = 0;
+  hip_check(carmel_hip_consolidate(device, n, src.data(), dst.data(), in.data(), out.data(), logw.data(), o.consolidate_max ? 1 : 0,
+                                   o.consolidate_unclamped ? 0 : 1, arc_map.data(), kept_id.data(), kept_logw.data(), &n_kept, &kms),
+            "carmel_hip_consolidate");
+  if (timing_on())
+    std::cerr << "timing: consolidate " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s (kernels "
+              << kms * 1e-3 << " s)\n";
+  const size_t st = M.states.size(), ar = M.num_arcs();
+  kept_id.resize(n_kept);
+  kept_logw.resize(n_kept);
+  M.consolidate(kept_id, kept_logw);
+  if (!o.flags[(unsigned)'d']) M.prune_useless();
+  if (!quiet && (M.states.size() != st || M.num_arcs() != ar))
+    std::cerr << "\t(" << st << " states / " << ar << " arcs consolidate-> " << M.states.size() << "/" << M.num_arcs() << ")" << std::endl;
+  return 0;
+}

@@ -49,6 +49,9 @@ static int print_help() {
                "pruning the composed machine before it is printed (also with -c or -F): --prune-paths=W (carmel's -w W) keeps the states "
                "and arcs on a path at most W times worse than the best path, --prune-states=N (carmel's -z N) at most N states, those "
                "of the best paths through them, --prune-arcs=W (carmel's -p W) no arc of a weight below W; "
+               "-C consolidates the composed machine first (before pruning, --best-paths=N or printing): arcs with the same source, "
+               "destination, input and output become one arc of their summed weight, at most 1; --consolidate-max keeps the largest "
+               "weight instead of the sum, --consolidate-unclamped lets a sum exceed 1; "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -174,6 +177,28 @@ static bool validate_pruning(const Options& o) {
   return true;
 }
 
+// consolidation (-C with --consolidate-max / --consolidate-unclamped: carmel's own names) applies to the composed machine that is
+// printed, pruned or listed: usage errors name the option, before any device call; true: consolidating
+static bool validate_consolidation(const Options& o) {
+  if (!o.flags[(unsigned)'C']) {
+    if (o.consolidate_max) throw UsageError("--consolidate-max applies to -C");
+    if (o.consolidate_unclamped) throw UsageError("--consolidate-unclamped applies to -C");
+    return false;
+  }
+  auto with = [&](bool on, const char* what) {
+    if (on) throw UsageError(std::string("-C with ") + what + " is not implemented: it consolidates the composed machine that is printed, pruned or listed, without lines or a corpus");
+  };
+  with(o.crp, "--crp");  // (which sets --train-cascade, which sets -t)
+  with(o.train_cascade, "--train-cascade");
+  with(o.flags[(unsigned)'t'], "-t");
+  with(o.flags[(unsigned)'S'], "-S");
+  with(o.flags[(unsigned)'b'], "-b");
+  with(o.flags[(unsigned)'i'], "-i");
+  with(o.have_generate_paths, "--generate-paths=N");
+  with(o.have_generate_pairs, "--generate-pairs=N");
+  return true;
+}
+
 // generation (--generate-paths=N / --generate-pairs=N: carmel's -G / -g): usage errors name the switch, before any device call;
 // true: generating
 static bool validate_generation(const Options& o) {
@@ -265,6 +290,7 @@ static int run(int argc, char** argv) {
   const bool scoring = !training && o.flags[(unsigned)'S'];  // carmel.cc:1134: -t overrides -S
   const bool with_pairs = training || scoring;
   if (o.flags[(unsigned)'h']) return print_help();
+  const bool consolidating = validate_consolidation(o);
   const bool pruning = validate_pruning(o);
   const bool listing = validate_best_paths(o);
   const bool generating = validate_generation(o);
@@ -285,6 +311,8 @@ static int run(int argc, char** argv) {
   j.wstyle = weight_style(o);
   if (int rc = load_members(j)) return rc;
   if (int rc = compose_members(j)) return rc;
+  if (consolidating)  // (the reference's order: consolidate, reduce, prune -- carmel_main::minimize before prune, carmel.cc:638-642)
+    if (int rc = consolidate_composition(o, *j.result, j.quiet, o.gpu)) return rc;
   if (decoding) return decode_batch(o, *j.result, line_text, j.wstyle, j.quiet, o.gpu);
   if (generating) return generate_batch(o, *j.result, j.wstyle, o.gpu);
   if (listing) return best_paths_batch(o, *j.result, j.wstyle, o.gpu);
@@ -292,7 +320,7 @@ static int run(int argc, char** argv) {
     if (int rc = prune_composition(o, *j.result, j.quiet, o.gpu)) return rc;
     return print_composition(j, !o.out_file.empty());
   }
-  if (!with_pairs) return print_composition(j);
+  if (!with_pairs) return print_composition(j, consolidating && !o.out_file.empty());
   read_corpus(j, corpus_text, /*weight_lines=*/!scoring);
   create_trainer(j);
   if (scoring) return score_pairs(j);

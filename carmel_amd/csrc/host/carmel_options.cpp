@@ -163,6 +163,10 @@ Options parse_args(int argc, char** argv) {
           throw UsageError("--prune-arcs=W needs a weight (arcs below it are discarded: carmel's -p W)");
         o.have_prune_arcs = true;
       }
+      else if (k == "consolidate-max")  // carmel's own (carmel.cc:1752): with -C, the largest weight of the duplicates, not their sum
+        o.consolidate_max = true;
+      else if (k == "consolidate-unclamped")  // carmel's own (carmel.cc:1753): with -C, a sum may exceed 1
+        o.consolidate_unclamped = true;
       else if (k == "generate-paths") {  // carmel's -G N under another name (carmel.cc:1446-1458): -G itself stays refused, below
         o.generate_paths = std::atol(v.c_str());
         o.have_generate_paths = true;
@@ -294,8 +298,9 @@ Options parse_args(int argc, char** argv) {
           default:
             // switches without a value that this front end implements; everything else carmel knows (k-best, generation,
             // projection, pruning, OpenFst, ...) is outside the training path
-            // (O I Q W E @: WFST::path_print, fst.h:60-160 -- how --print-to writes the sampled paths; b s r i: batch decoding)
-            if (!std::strchr("tUujnlqdKmHJZDB2?:caShOIQWE@1bsri", a[j]))
+            // (O I Q W E @: WFST::path_print, fst.h:60-160 -- how --print-to writes the sampled paths; b s r i: batch decoding;
+            // C: consolidating the composed machine's duplicate arcs)
+            if (!std::strchr("tUujnlqdKmHJZDB2?:caShOIQWE@1bsriC", a[j]))
               throw UsageError(std::string("switch -") + a[j] + " is not implemented by the GPU training front end");
             break;
         }

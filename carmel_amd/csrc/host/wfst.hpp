@@ -285,6 +285,24 @@ class Transducer {
     return true;
   }
 
+  // keep the arcs kept_id names (arc ids in flatten's order, ascending: the representatives of carmel_hip_consolidate's segments),
+  // each with its new weight, in list order; every other arc goes, the arcs of weight zero among them.  The kept arc's symbols
+  // and tie group are its own: the first arc's of its segment, as the reference leaves them (State::reduce, state.h:248-278).
+  void consolidate(const std::vector<uint32_t>& kept_id, const std::vector<double>& kept_logw) {
+    size_t id = 0, k = 0;
+    for (auto& st : states) {
+      std::vector<HArc> kept;
+      for (auto a : st) {
+        if (k < kept_id.size() && kept_id[k] == id) {
+          a.logw = kept_logw[k++];
+          kept.push_back(a);
+        }
+        ++id;
+      }
+      st.swap(kept);
+    }
+  }
+
   // ---- writer (wfstio.cc:594-625) ----
   std::string to_text(bool full /*-J*/, bool arc_per_line /*-H*/, int wstyle, bool include_zero = false) const {
     std::string o = state_name(final_state);

@@ -24,7 +24,9 @@ const char* const kKeys[] = {
     // batch decoding (decode.hip): "0" puts the trellis rows in global memory for any |Q|; the back-pointer budget of a chunk of lines
     "decode_lds", "decode_chunk_bytes",
     // the K best paths of the whole machine (decode_best_paths.hip): states of more in-arcs than this are merged by a wavefront
-    "best_paths_wave_degree"};
+    "best_paths_wave_degree",
+    // consolidating duplicate arcs (consolidate.hip): segments of more members than this are summed by a wavefront
+    "consolidate_wave_members"};
 constexpr int kN = (int)(sizeof kKeys / sizeof kKeys[0]);
 const char* volatile g_val[kN];  // interned strings (a replaced value is not freed: a reader may still hold it)
 std::mutex g_mu;

@@ -19,6 +19,7 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     state_keep, arc_keep = d.prune(log_ratio, max_states, min_arc_logw)   # what stays of the machine (carmel -w / -z / -p; csrc/decode_prune.hip)
     F, R = d.prune_distances()                     # the best distance from state 0 to every state and from every state to the final one
     d.set_weights(logw); d.close()
+    w2, arc_map, ms = consolidate(wfst, mode="sum", clamp=True)   # duplicate arcs merged (carmel -C; csrc/consolidate.hip): no decoder needed
 
 best[l] is the natural log of line l's best path weight (-inf: no derivation); paths[l] its arc ids in path order.
 weights[l] holds the reported ln weights of line l's min(k, number of derivations) best derivations, best first, and kpaths[l]
@@ -295,3 +296,33 @@ class Decoder(object):
             self.close()
         except Exception:
             pass
+
+
+CONSOLIDATE_MODES = {"sum": 0, "max": 1}
+
+
+def consolidate_raw(src, dst, isym, osym, logw, mode="sum", clamp=True, device=0):
+    """-> (n_kept, kept_id, kept_logw, arc_map, kernel_ms): the arrays of carmel_hip_consolidate (include/carmel_hip.h has the
+    rule), kept_id and kept_logw cut to n_kept entries"""
+    src, dst, isym, osym, logw = u32(src), u32(dst), u32(isym), u32(osym), f64(logw)
+    n = len(src)
+    assert all(len(a) == n for a in (dst, isym, osym, logw))
+    arc_map, kept_id, kept_logw = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1))
+    n_kept, ms = C.c_uint64(), C.c_double()
+    check(lib.carmel_hip_consolidate(int(device), n, ptr(src), ptr(dst), ptr(isym), ptr(osym), ptr(logw), CONSOLIDATE_MODES[mode],
+                                     1 if clamp else 0, ptr(arc_map), ptr(kept_id), ptr(kept_logw), C.byref(n_kept), C.byref(ms)),
+          "carmel_hip_consolidate")
+    k = n_kept.value
+    return k, kept_id[:k], kept_logw[:k], arc_map[:n], ms.value
+
+
+def consolidate(wfst, mode="sum", clamp=True, device=0):
+    """-> (Wfst, arc_map, kernel_ms): arcs of the same source, destination, input and output merged into one (carmel -C;
+    csrc/consolidate.hip), of their summed weight (mode "sum"; at most 1 with clamp) or of their largest weight (mode "max":
+    carmel --consolidate-max).  The new machine's arcs are the first arc of every such set, in the old order, with that arc's
+    symbols and tie group; arc_map[a] is old arc a's new id, 0xffffffff for an arc of weight zero, which goes."""
+    from .model import Wfst
+    _, kept_id, kept_logw, arc_map, ms = consolidate_raw(wfst.src, wfst.dst, wfst.isym, wfst.osym, wfst.logw, mode, clamp, device)
+    new = Wfst(wfst.n_states, wfst.final, wfst.src[kept_id], wfst.dst[kept_id], wfst.isym[kept_id], wfst.osym[kept_id], kept_logw,
+               wfst.group[kept_id])
+    return new, arc_map, ms

@@ -831,6 +831,36 @@ int carmel_hip_decoder_prune_distances(carmel_hip_decoder* d, double* fwd, doubl
 /* the last successful prune call: the rounds of the forward and of the backward pass */
 int carmel_hip_decoder_prune_stats(carmel_hip_decoder* d, uint32_t* fwd_rounds, uint32_t* bwd_rounds);
 
+/* ---- consolidating duplicate arcs (carmel -C, --consolidate-max, --consolidate-unclamped; csrc/consolidate.hip) ----
+ * Replaces: WFST::consolidateArcs (fst.cc:526-528) and State::reduce (state.h:248-278), called from carmel_main::minimize
+ * (carmel.cc:638-642; the two long options: carmel.cc:1752-1753).  Free-standing: no handle.  The rule:
+ * Inputs.  n_arcs arcs in arc-id order with src non-decreasing, as Transducer::flatten gives them.  Per arc: src, dst, in_sym,
+ * out_sym as u32, any value up to 0xfffffffe, and logw.  mode: 0 = sum, 1 = max.  clamp: 0 or 1; it is read in sum mode only.
+ * Existence.  An arc exists iff logw > -inf.  A NaN or +inf weight, src not non-decreasing, or n_arcs >= 0xffffffff is
+ * CARMEL_HIP_ERR_ARG, and nothing is written (so is a state or symbol of 0xffffffff, a null buffer, a mode or clamp other than
+ * 0 or 1).
+ * Segment.  A segment is all existing arcs with equal (src, dst, in_sym, out_sym), all four fields, full 32 bits each.  Tie groups
+ * play no part (the reference's UnArc has none either).
+ * Representative.  The member with the lowest arc id (the reference keeps the first arc in list order and erases the later ones).
+ * Weight of a segment.  A segment of one member keeps that member's weight bit for bit, in every mode.  Max mode: the largest
+ * member weight, a copy of a member's bits, so exact.  Sum mode: ln sum exp(w_i), computed with sweep_math.hpp's Lse in a fixed
+ * order, so that two calls return the same bytes: a segment of at most `consolidate_wave_members` members (option, default 64) in
+ * arc-id order by one lane; a larger one by a wavefront, lane l taking members l, l + 64, ... in that order and six shuffle steps
+ * combining the lanes' (m, acc) pairs in a fixed tree.  With clamp, a result > 0.0 becomes 0.0 (the reference clamps after every
+ * add; for non-negative terms that equals one clamp at the end).
+ * Result.  *n_kept is the number of segments.  New arc j (0 <= j < n_kept) is the segment with the j-th smallest representative
+ * id: the result is still state-major, with each state's survivors in first-occurrence order, as the reference leaves them.
+ * kept_id[j] is that representative's old arc id, kept_logw[j] the segment's weight, arc_map[a] the new index of arc a's segment,
+ * or 0xffffffff for an arc that does not exist.  kept_id and kept_logw are caller buffers of n_arcs entries; entries from n_kept
+ * on are not written.
+ * Deviations from the reference: the total order above replaces hash-table iteration side effects.  There are no others.
+ * No float atomics are used.  Without a device: CARMEL_HIP_ERR_HIP (there is no CPU fallback).  kernel_ms (nullable): HIP events
+ * around the kernels, not the copies. */
+int carmel_hip_consolidate(int device, uint64_t n_arcs, const uint32_t* src, const uint32_t* dst, const uint32_t* in_sym,
+                           const uint32_t* out_sym, const double* logw, int mode, int clamp,
+                           uint32_t* arc_map /* [n_arcs] */, uint32_t* kept_id /* [n_arcs] */, double* kept_logw /* [n_arcs] */,
+                           uint64_t* n_kept, double* kernel_ms /* nullable: HIP events around the kernels, not the copies */);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;
