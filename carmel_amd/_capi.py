@@ -55,6 +55,10 @@ SYMBOLS = [
     "carmel_hip_decoder_prune_distances",
     "carmel_hip_decoder_prune_stats",
     "carmel_hip_consolidate",
+    "carmel_hip_decoder_machine_sums",
+    "carmel_hip_decoder_machine_sums_states",
+    "carmel_hip_decoder_machine_sums_arcs",
+    "carmel_hip_decoder_machine_sums_stats",
 ]
 
 
@@ -260,6 +264,10 @@ def _load():
     lib.carmel_hip_decoder_prune_distances.argtypes = [vp, vp, vp]
     lib.carmel_hip_decoder_prune_stats.argtypes = [vp, vp, vp]
     lib.carmel_hip_consolidate.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.carmel_hip_decoder_machine_sums.argtypes = [vp, vp, vp, vp]
+    lib.carmel_hip_decoder_machine_sums_states.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.carmel_hip_decoder_machine_sums_arcs.argtypes = [vp, vp]
+    lib.carmel_hip_decoder_machine_sums_stats.argtypes = [vp, vp, vp]
     for s in SYMBOLS:  # a prototype for every entry point: without one ctypes passes Python ints as C int (64-bit seeds
         if getattr(lib, s).argtypes is None:  # and bare handles would be truncated)
             raise ImportError("carmel_amd: no ctypes prototype for %s" % s)

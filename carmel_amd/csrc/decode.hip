@@ -229,6 +229,7 @@ int carmel_hip_decoder_set_weights(carmel_hip_decoder* d, const double* logw) {
   d->gen_ready = false;  // (the generation tables hold the old weights' sums: the next carmel_hip_decoder_generate rebuilds them)
   d->bp_ready = false;   // (and the next carmel_hip_decoder_best_paths its own)
   d->pr_ready = false;   // (and the next carmel_hip_decoder_prune)
+  d->ms_ready = false;   // (and the next carmel_hip_decoder_machine_sums)
   return d->upload_tables();  // (which arcs have weight zero may have changed)
 }
 

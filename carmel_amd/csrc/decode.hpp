@@ -1,7 +1,8 @@
 // decode.hpp — what the batch decoders (1-best decode.hip, k-best decode_kbest.hip, all-paths sums decode_sum.hip, posterior
 // samples decode_sample.hip, arc posteriors decode_posterior.hip, pairs decode_pairs.hip, decode_pairs_posterior.hip,
 // decode_pairs_sample.hip and decode_pairs_kbest.hip; generation, decode_generate.hip, and the whole machine's K best paths,
-// decode_best_paths.hip, take the handle and the path store; its pruning, decode_prune.hip, the handle) share: the prepared tables, the decoder
+// decode_best_paths.hip, take the handle and the path store; its pruning, decode_prune.hip, and its sums over all paths,
+// decode_machine_sums.hip, the handle) share: the prepared tables, the decoder
 // handle, the constants, the arguments every trellis kernel takes, and the host drivers of decode_paths.hip -- the chunk driver of all entry points,
 // the path driver of the two that return a trellis' recorded paths, and the assembly of a chunk's paths.  The tables are built on
 // the host by build_decode_tables (decode_tables.hpp) and copied to the device by carmel_hip_decoder::upload_tables (decode.hip);
@@ -211,6 +212,18 @@ struct carmel_hip_decoder {
   DevBuf<double> pr_f64[2];
   std::vector<double> pr_fwd, pr_bwd;
   uint32_t pr_rounds[2] = {0, 0};
+  // the sums over all paths of the whole machine (carmel_hip_decoder_machine_sums, decode_machine_sums.hip): the tables of the
+  // machine and of its reversal, built and copied by the first call, dropped by carmel_hip_decoder_set_weights; the last
+  // successful call's results
+  bool ms_ready = false, ms_have = false;
+  carmel_hip::BestPathsTables MS[2];  // forward, backward
+  DevBuf<uint32_t> ms_u32[10], ms_dst;  // ms_dst: every arc's destination, beside a_src
+  DevBuf<double> ms_f64[2];
+  std::vector<double> ms_alpha, ms_beta, ms_cf, ms_cb, ms_post;
+  std::vector<uint32_t> ms_level;
+  double ms_total = 0, ms_paths = 0;
+  uint64_t ms_useful = 0;
+  uint32_t ms_levels[2] = {0, 0};
   double last_ms = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

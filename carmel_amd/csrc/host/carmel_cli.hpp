@@ -127,6 +127,11 @@ struct Options {
   // output become one arc of their summed weight (carmel_hip_consolidate); --consolidate-max keeps the largest weight instead,
   // --consolidate-unclamped lets a sum exceed 1
   bool consolidate_max = false, consolidate_unclamped = false;
+  // --machine-sums: in place of the composed machine, the number of its paths and the sum of their weights
+  // (carmel_hip_decoder_machine_sums); --machine-counts=FILE implies it and writes the machine with every arc's expected count
+  // under the machine's own path distribution as its weight
+  bool machine_sums = false, have_machine_counts = false;
+  std::string machine_counts;
   bool sum = false;  // --sum-paths with -b / -i (carmel's --sum): the report also multiplies the lines' sums of all paths (report_batch, carmel.cc:354-377)
   std::vector<const char*> files;
 };
@@ -198,6 +203,7 @@ int generate_batch(const Options& o, carmel_host::Transducer& M, int ws, int dev
 int best_paths_batch(const Options& o, carmel_host::Transducer& M, int ws, int device);
 int prune_composition(const Options& o, carmel_host::Transducer& M, bool quiet, int device);
 int consolidate_composition(const Options& o, carmel_host::Transducer& M, bool quiet, int device);
+int machine_sums_composition(const Options& o, carmel_host::Transducer& M, int ws, int device);
 void log_lattice_stats(const carmel_hip_lattice_stats& ls, size_t n);      // carmel_em.cpp
 void train_em(Job& j, const Options& iteration_controls);
 int train_gibbs(Job& j);                                                   // carmel_gibbs.cpp

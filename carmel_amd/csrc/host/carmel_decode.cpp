@@ -599,3 +599,65 @@ int consolidate_composition(const Options& o, Transducer& M, bool quiet, int dev
     std::cerr << "\t(" << st << " states / " << ar << " arcs consolidate-> " << M.states.size() << "/" << M.num_arcs() << ")" << std::endl;
   return 0;
 }
+
+// --machine-sums / --machine-counts=FILE (carmel's --sum without -b / -i: sum_acyclic_paths on the result, carmel.cc:555-599, and the
+// third line of -c, carmel.cc:841-855): the composed machine, consolidated and pruned if that was asked for, is flattened and
+// carmel_hip_decoder_machine_sums (csrc/decode_machine_sums.hip) sums over all its paths.  Two lines go to stdout, or to the -F
+// file, in place of the transducer; with -c they follow -c's own two lines.  --machine-counts=FILE writes the machine as --posterior-counts does (-H / -J apply, every arc written), every arc's
+// weight replaced by its expected number of uses on a path drawn with probability weight / sum; an arc on no path gets 0.  A cycle
+// among the states on a path is the library's error (exit -11).
+int machine_sums_composition(const Options& o, Transducer& M, int ws, int device) {
+  double total = kNegInf, n_paths = 0;
+  std::vector<double> post(std::max<size_t>(M.num_arcs(), 1), kNegInf);
+  if (!M.states.empty()) {  // (an empty machine has no path)
+    std::vector<uint32_t> src, dst, in, out, group;
+    std::vector<double> logw;
+    M.flatten(src, dst, in, out, logw, group);
+    carmel_hip_decoder* d = 0;
+    hip_check(carmel_hip_decoder_create(&d, device, (uint32_t)M.states.size(), M.final_state, logw.size(), src.data(), dst.data(),
+                                        in.data(), out.data(), logw.data(), 0),
+              "carmel_hip_decoder_create");
+    struct Guard {
+      carmel_hip_decoder* d;
+      ~Guard() { carmel_hip_decoder_destroy(d); }
+    } guard{d};
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t n_useful = 0;
+    hip_check(carmel_hip_decoder_machine_sums(d, &total, &n_paths, &n_useful), "carmel_hip_decoder_machine_sums");
+    if (o.have_machine_counts) hip_check(carmel_hip_decoder_machine_sums_arcs(d, post.data()), "carmel_hip_decoder_machine_sums_arcs");
+    if (timing_on()) {
+      double kms = 0;
+      uint32_t fl = 0, bl = 0;
+      carmel_hip_decoder_last_ms(d, &kms);
+      carmel_hip_decoder_machine_sums_stats(d, &fl, &bl);
+      std::cerr << "timing: machine sums " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s (kernels "
+                << kms * 1e-3 << " s, " << n_useful << " useful states, " << fl << " forward levels, " << bl << " backward levels)\n";
+    }
+  }
+  char count[64];
+  if (n_paths < 9007199254740992.0)  // (exact below 2^53)
+    std::snprintf(count, sizeof count, "%llu", (unsigned long long)n_paths);
+  else
+    std::snprintf(count, sizeof count, "%.17g", n_paths);
+  std::ofstream of;
+  if (!o.out_file.empty()) {  // -F names where the result goes, as for the transducer these lines stand in for
+    of.open(o.out_file.c_str());
+    if (!of) {
+      std::cerr << "Could not create file " << o.out_file << ".\n";
+      return -8;
+    }
+  }
+  std::ostream& os = o.out_file.empty() ? static_cast<std::ostream&>(std::cout) : of;
+  if (o.flags[(unsigned)'c'])  // -c's two lines come first, unchanged
+    os << "Number of states in result: " << M.states.size() << "\nNumber of arcs in result: " << M.num_arcs() << "\n";
+  os << "Number of paths in result: " << count << "\nSum of all paths in result: " << format_weight(total, ws) << "\n" << std::flush;
+  if (o.have_machine_counts) {
+    Transducer counted(M);
+    counted.set_weights(post.data());
+    std::ofstream of(o.machine_counts.c_str());
+    of << counted.to_text(o.flags[(unsigned)'J'], o.flags[(unsigned)'H'], ws, /*include_zero=*/true);
+    of.close();
+    if (!of) throw std::runtime_error("--machine-counts: cannot write " + o.machine_counts);
+  }
+  return 0;
+}

@@ -52,6 +52,10 @@ static int print_help() {
                "-C consolidates the composed machine first (before pruning, --best-paths=N or printing): arcs with the same source, "
                "destination, input and output become one arc of their summed weight, at most 1; --consolidate-max keeps the largest "
                "weight instead of the sum, --consolidate-unclamped lets a sum exceed 1; "
+               "--machine-sums prints, in place of the composed machine (after -C and --prune-*), the number of its paths and the sum of "
+               "their weights (carmel's --sum without -b / -i; no cycles among the states on a path; to the -F file if one is named, after "
+               "-c's two lines with -c); --machine-counts=FILE also writes "
+               "the machine with every arc's expected count over its own paths as its weight; "
                "the full list and what each replaces: INTEGRATION.md\n";
   return 0;
 }
@@ -199,6 +203,33 @@ static bool validate_consolidation(const Options& o) {
   return true;
 }
 
+// the sums over all paths of the composed machine (--machine-sums, --machine-counts=FILE): usage errors name the option, before any
+// device call; true: summing
+static bool validate_machine_sums(const Options& o) {
+  if (!o.machine_sums) return false;
+  const char* sw = o.have_machine_counts ? "--machine-counts=FILE" : "--machine-sums";
+  if (o.have_machine_counts && o.machine_counts.empty()) throw UsageError("--machine-counts=FILE needs a file name");
+  auto with = [&](bool on, const char* what) {
+    if (on) throw UsageError(std::string(sw) + " with " + what + " is not implemented: it sums over the paths of the composed machine, without lines or a corpus");
+  };
+  with(o.flags[(unsigned)'b'], "-b");
+  with(o.flags[(unsigned)'i'], "-i");
+  with(o.flags[(unsigned)'s'], "-s");
+  with(o.flags[(unsigned)'r'], "-r");
+  with(o.crp, "--crp");  // (which sets --train-cascade, which sets -t)
+  with(o.train_cascade, "--train-cascade");
+  with(o.flags[(unsigned)'t'], "-t");
+  with(o.flags[(unsigned)'S'], "-S");
+  with(o.kpaths != 0, "-k");
+  with(o.have_best_paths, "--best-paths=N");
+  with(o.have_generate_paths, "--generate-paths=N");
+  with(o.have_generate_pairs, "--generate-pairs=N");
+  with(o.have_generate_max_arcs, "--generate-max-arcs=L");
+  with(o.have_generate_tries, "--generate-tries=T");
+  with(o.have_pair_lines, "--pair-lines=FILE");
+  return true;
+}
+
 // generation (--generate-paths=N / --generate-pairs=N: carmel's -G / -g): usage errors name the switch, before any device call;
 // true: generating
 static bool validate_generation(const Options& o) {
@@ -290,6 +321,7 @@ static int run(int argc, char** argv) {
   const bool scoring = !training && o.flags[(unsigned)'S'];  // carmel.cc:1134: -t overrides -S
   const bool with_pairs = training || scoring;
   if (o.flags[(unsigned)'h']) return print_help();
+  const bool summing = validate_machine_sums(o);
   const bool consolidating = validate_consolidation(o);
   const bool pruning = validate_pruning(o);
   const bool listing = validate_best_paths(o);
@@ -318,8 +350,9 @@ static int run(int argc, char** argv) {
   if (listing) return best_paths_batch(o, *j.result, j.wstyle, o.gpu);
   if (pruning) {
     if (int rc = prune_composition(o, *j.result, j.quiet, o.gpu)) return rc;
-    return print_composition(j, !o.out_file.empty());
+    if (!summing) return print_composition(j, !o.out_file.empty());
   }
+  if (summing) return machine_sums_composition(o, *j.result, j.wstyle, o.gpu);
   if (!with_pairs) return print_composition(j, consolidating && !o.out_file.empty());
   read_corpus(j, corpus_text, /*weight_lines=*/!scoring);
   create_trainer(j);

@@ -186,7 +186,13 @@ Options parse_args(int argc, char** argv) {
       else if (k == "sum-paths")  // not a carmel option: carmel's --sum with batch decoding (carmel.cc:555-599), every line's sum
         o.sum = true;             // of all paths (carmel_hip_decode_sum); --sum itself stays refused, below
       else if (k == "sum")
-        throw UsageError("option --sum is not implemented under that name; with -b or -i use --sum-paths");
+        throw UsageError("option --sum is not implemented under that name; with -b or -i use --sum-paths, for the sum over all paths of the composed machine itself --machine-sums");
+      else if (k == "machine-sums")  // carmel's --sum without -b / -i (carmel.cc:555-599) and the third line of -c (carmel.cc:841-855)
+        o.machine_sums = true;
+      else if (k == "machine-counts") {  // not a carmel option: every arc's expected count over the machine's own paths
+        o.machine_counts = v;
+        o.have_machine_counts = o.machine_sums = true;
+      }
       else if (k == "disk-cache-derivations") {
         // carmel.cc:243-246, fst.h:1057-1076: the reference spills its derivation cache to disk when it outgrows memory (and
         // without -? rebuilds every pair's derivations in every iteration, cached_derivs.h:60-101).  Here: when the lattices of

@@ -26,7 +26,9 @@ const char* const kKeys[] = {
     // the K best paths of the whole machine (decode_best_paths.hip): states of more in-arcs than this are merged by a wavefront
     "best_paths_wave_degree",
     // consolidating duplicate arcs (consolidate.hip): segments of more members than this are summed by a wavefront
-    "consolidate_wave_members"};
+    "consolidate_wave_members",
+    // the sums over all paths of the whole machine (decode_machine_sums.hip): states of more useful in-arcs than this are summed by a wavefront
+    "machine_sums_wave_degree"};
 constexpr int kN = (int)(sizeof kKeys / sizeof kKeys[0]);
 const char* volatile g_val[kN];  // interned strings (a replaced value is not freed: a reader may still hold it)
 std::mutex g_mu;

@@ -18,6 +18,8 @@ and csrc/decode_posterior.hip, on the drivers of csrc/decode_paths.hip).
     kbest = d.best_paths(k)                        # the k best paths of the machine itself, best first (carmel -k n; csrc/decode_best_paths.hip)
     state_keep, arc_keep = d.prune(log_ratio, max_states, min_arc_logw)   # what stays of the machine (carmel -w / -z / -p; csrc/decode_prune.hip)
     F, R = d.prune_distances()                     # the best distance from state 0 to every state and from every state to the final one
+    Z, N, n_useful = d.machine_sums()              # the ln of the sum over all paths of the machine, and their number (csrc/decode_machine_sums.hip)
+    alpha, beta, cf, cb, level = d.machine_sums_states(); ln_gamma = d.machine_sums_arcs()   # per state, and every arc's ln posterior
     d.set_weights(logw); d.close()
     w2, arc_map, ms = consolidate(wfst, mode="sum", clamp=True)   # duplicate arcs merged (carmel -C; csrc/consolidate.hip): no decoder needed
 
@@ -267,6 +269,36 @@ class Decoder(object):
         """-> (forward rounds, backward rounds) of the last prune call"""
         f, b = C.c_uint32(), C.c_uint32()
         check(lib.carmel_hip_decoder_prune_stats(self._h, C.byref(f), C.byref(b)), "carmel_hip_decoder_prune_stats")
+        return f.value, b.value
+
+    def machine_sums(self):
+        """-> (total_logw, n_paths, n_useful): the ln of the sum over ALL paths of the machine from state 0 to the final state
+        (-inf: none), their number (an f64, exact below 2^53) and the number of states on such a path
+        (carmel_hip_decoder_machine_sums; include/carmel_hip.h has the rule).  A cycle among those states: CarmelHipError"""
+        z, n, u = C.c_double(), C.c_double(), C.c_uint64()
+        check(lib.carmel_hip_decoder_machine_sums(self._h, C.byref(z), C.byref(n), C.byref(u)), "carmel_hip_decoder_machine_sums")
+        return z.value, n.value, u.value
+
+    def machine_sums_states(self):
+        """-> (alpha, beta, paths_to, paths_from, level) of the last machine_sums call, per state: the ln of the sum over the paths
+        from state 0 to it and from it to the final state, their numbers, and its level (0xffffffff: not on a path)"""
+        Q = self.n_states
+        alpha, beta, cf, cb, level = np.empty(Q), np.empty(Q), np.empty(Q), np.empty(Q), np.empty(Q, np.uint32)
+        check(lib.carmel_hip_decoder_machine_sums_states(self._h, ptr(alpha), ptr(beta), ptr(cf), ptr(cb), ptr(level)),
+              "carmel_hip_decoder_machine_sums_states")
+        return alpha, beta, cf, cb, level
+
+    def machine_sums_arcs(self):
+        """-> per arc the ln of its expected number of uses on a path drawn with probability weight / sum (-inf: on no path), of
+        the last machine_sums call"""
+        post = np.full(max(self.n_arcs, 1), -np.inf)
+        check(lib.carmel_hip_decoder_machine_sums_arcs(self._h, ptr(post)), "carmel_hip_decoder_machine_sums_arcs")
+        return post[:self.n_arcs]
+
+    def machine_sums_stats(self):
+        """-> (forward levels, backward levels) of the last machine_sums call"""
+        f, b = C.c_uint32(), C.c_uint32()
+        check(lib.carmel_hip_decoder_machine_sums_stats(self._h, C.byref(f), C.byref(b)), "carmel_hip_decoder_machine_sums_stats")
         return f.value, b.value
 
     def posterior(self, lines, weights=None):

@@ -861,6 +861,54 @@ int carmel_hip_consolidate(int device, uint64_t n_arcs, const uint32_t* src, con
                            uint32_t* arc_map /* [n_arcs] */, uint32_t* kept_id /* [n_arcs] */, double* kept_logw /* [n_arcs] */,
                            uint64_t* n_kept, double* kernel_ms /* nullable: HIP events around the kernels, not the copies */);
 
+/* ---- the sum over all paths of the whole machine, its path count and arc posteriors (csrc/decode_machine_sums.hip) ----
+ * Replaces: WFST::sum_acyclic_paths, carmel's --sum outside batch mode (carmel.cc:555-599, fst.h:1183-1191, graph.h:391-419), and
+ * WFST::numNoCyclePaths, the third line of carmel -c (carmel.cc:841-855, fst.h:1166-1174, graph.h:363-378); the arc posteriors are
+ * an addition.  No lines are given; arc and state ids are those of carmel_hip_decoder_create.  The rule:
+ * Arcs.  Only arcs of log weight > -inf exist.  Symbols and `side` play no part.  Log weights above 0 are legal: there are no
+ * cycles to amplify them.
+ * Useful states U.  q is in U iff q is reachable from state 0 and the final state is reachable from q, over existing arcs.  Useful
+ * arcs are the existing arcs with both ends in U.  If the final state is not reachable, U is empty.  Cycles outside U (on reachable
+ * dead ends, in unreachable parts, self-loops there) are harmless.
+ * Levels.  U is peeled by in-degree over the useful arcs: state 0 has level 0, level(q) = 1 + max level(src a) over the useful arcs
+ * a into q.  A useful state that never reaches in-degree 0 lies on or behind a cycle inside U: CARMEL_HIP_ERR_UNSUPPORTED, the
+ * message names the lowest-numbered such state ("state N lies on or behind a cycle ..."), and the handle's earlier results stay.
+ * A useful self-loop is a cycle, and so is a useful arc into state 0 or out of the final state.  The backward levels come from the
+ * same peeling of the reversed useful machine, started at the final state.
+ * Forward sum.  alpha[0] = 0.0.  For q in U, q != 0: alpha[q] = Lse (csrc/sweep_math.hpp) over q's useful in-arcs of
+ * (alpha[src a] + w(a)) in a fixed order: a state of at most `machine_sums_wave_degree` useful in-arcs (option, default 32) by one
+ * lane in arc-id order; a state of more by a wavefront, lane l taking positions l, l + 64, ... of the state's list of existing
+ * in-arcs (in arc-id order; an arc that is not useful has a term of -inf, which Lse passes over), then six shuffle steps combining
+ * the lanes' (m, acc) pairs in a fixed tree, as carmel_hip_consolidate does.  A state with one useful in-arc gets alpha[src] + w
+ * bit for bit.  alpha = -inf outside U.
+ * Backward sum.  The same on the reversed machine: beta[final] = 0.0, the terms are w(a) + beta[dst a], a state's out-arcs in
+ * arc-id order.
+ * Total.  Z = alpha[final]; beta[0] is a second estimate of the same number, returned in the per-state array.
+ * Path counts.  cf[0] = 1.0, cf[q] = the sum of cf[src a] over the useful in-arcs, plain f64 additions in the order of the sum
+ * beside them; the two forms differ only above 2^53, below which the counts are exact.  cb is the same backwards; N = cf[final].
+ * Arc posterior.  ln gamma(a) = ((alpha[src a] + w(a)) + beta[dst a]) - Z for a useful arc, -inf otherwise; the expected number of
+ * uses of the arc on a path drawn with probability weight / sum is exp of that, which is left to the caller.
+ * Empty cases.  U empty: success, Z = -inf, N = 0, every sum -inf, every count 0, every level 0xffffffff.  The final state being
+ * state 0 with nothing useful looping through it: Z = 0.0, N = 1.
+ * Determinism.  No float atomics; for one value of the option two calls return the same bytes; the results do not depend on
+ * worklist order or launch geometry.
+ * Deviations from the reference: on a cyclic machine it drops the back arcs its depth-first search happens to meet, and warns;
+ * here a cycle inside U is refused.  It counts paths in its log-float Weight and counts arcs of weight 0 too; here only existing
+ * arcs count, in f64.
+ * total_logw, n_paths and n_useful (|U|) may be null.  More than |Q| + 1 rounds in any loop: CARMEL_HIP_ERR_STATE.
+ * CARMEL_HIP_ERR_ARG: a null handle.  May alternate with every other entry point on one handle, and sees the weights of
+ * carmel_hip_decoder_set_weights (its tables are built on the first call and dropped there); carmel_hip_decoder_last_ms covers
+ * its kernels. */
+int carmel_hip_decoder_machine_sums(carmel_hip_decoder* d, double* total_logw, double* n_paths, uint64_t* n_useful);
+/* the last successful machine_sums call's alpha, beta, cf, cb (n_states doubles each) and forward levels (0xffffffff outside U);
+ * every pointer may be null.  CARMEL_HIP_ERR_STATE before any successful call. */
+int carmel_hip_decoder_machine_sums_states(carmel_hip_decoder* d, double* alpha, double* beta, double* paths_to, double* paths_from,
+                                           uint32_t* fwd_level);
+/* the last successful machine_sums call's ln gamma, n_arcs doubles */
+int carmel_hip_decoder_machine_sums_arcs(carmel_hip_decoder* d, double* log_posterior);
+/* the last successful machine_sums call: the number of forward and of backward levels (0 when U is empty) */
+int carmel_hip_decoder_machine_sums_stats(carmel_hip_decoder* d, uint32_t* fwd_levels, uint32_t* bwd_levels);
+
 /* ---- host-only inspection (no GPU needed): the lattice image carmel_hip_build_lattices uploads ----
  * Used by the CPU test-suite to check lattice construction and layout against the oracle. */
 typedef struct carmel_hip_host_lattices carmel_hip_host_lattices;

@@ -12,7 +12,7 @@ for f in kernels.hip tile_sweep.hip engine.cpp engine_unrolled.cpp compose.hip m
   /opt/rocm/bin/hipcc $CXX $HIPFLAGS "$@" -c $f -o $OUT/${f%.*}.o & pids+=($!)
 done
 /opt/rocm/bin/hipcc $CXX $HIPFLAGS -mllvm -disable-machine-licm "$@" -c mstep_wide.hip -o $OUT/mstep_wide.o & pids+=($!)  # (Makefile: WIDEFLAGS)
-for f in gibbs_exact.hip gibbs_lane.hip gibbs.hip forest_exact.hip forest.hip forest_host.cpp forest_gibbs.cpp decode.hip decode_paths.hip decode_kbest.hip decode_sum.hip decode_sample.hip decode_posterior.hip decode_pairs.hip decode_pairs_posterior.hip decode_pairs_sample.hip decode_pairs_kbest.hip decode_generate.hip decode_generate_tables.cpp decode_tables.cpp decode_best_paths.hip decode_best_paths_tables.cpp decode_prune.hip consolidate.hip; do
+for f in gibbs_exact.hip gibbs_lane.hip gibbs.hip forest_exact.hip forest.hip forest_host.cpp forest_gibbs.cpp decode.hip decode_paths.hip decode_kbest.hip decode_sum.hip decode_sample.hip decode_posterior.hip decode_pairs.hip decode_pairs_posterior.hip decode_pairs_sample.hip decode_pairs_kbest.hip decode_generate.hip decode_generate_tables.cpp decode_tables.cpp decode_best_paths.hip decode_best_paths_tables.cpp decode_prune.hip consolidate.hip decode_machine_sums.hip; do
   /opt/rocm/bin/hipcc $CXX $HIPFLAGS -ffp-contract=off "$@" -c $f -o $OUT/${f%.*}.o & pids+=($!)
 done
 /opt/rocm/bin/hipcc $CXX "$@" -c unrolled.cpp -o $OUT/unrolled_host.o & pids+=($!)
